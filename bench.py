@@ -2,17 +2,21 @@
 """Headline benchmark: Mpixel/s forward+backward of the hash-grid encoder path (coords -> encoder -> decoder ->
 MSE gradient -> decoder/table gradients) at L=16, F=2, T=2^19, batch 2^20 pixels per GPU (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up the headline mode, warms up, times exactly K steps and prints one JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  --dump-outputs DIR then also writes what the last timed step computed (see
+dump_outputs).  Everything else the benchmark measures or checks runs only under --full (described below).
 
 N > 1: one rank per GPU over RCCL.  Launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
 (WORLD_SIZE set), or bare (`python bench.py --gpus N`): the parent then starts the N ranks itself — before it has touched
 the GPU — and exits with their status.  A WORLD_SIZE that disagrees with --gpus is refused.
 
-One JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, HIP-event timed on the
-launch stream), `roofline_encoder`, `roofline_step` and `cpu_baseline` (CPU oracle timed on the host cores, bounded
-sample, rank 0, N=1 only).
+--full adds to the line `roofline` (dominant kernel, HIP-event timed on the launch stream), `roofline_encoder`, `kernel_ms`,
+`cpu_baseline` (CPU oracle timed on the host cores, bounded sample, rank 0, N=1 only), the measured streaming-copy bandwidth,
+five more timing windows, the exchange model, the with-Adam / full-output variants of the step and the other modes.
 
-Modes (--mode picks the headline; the others are reported in the same line under "modes"):
+Modes (--mode picks the headline; with --full the others are reported in the same line under "modes"):
   gngf_frozen    cfg2, GNGF indexing with a frozen HashProbDistribution (the reference's -hwp mode, models.py:364-371):
                  the per-vertex top-K table is a function of frozen weights and is rebuilt only when they change.
   gngf_learning  cfg2, GNGF indexing with a trainable HPD: every step re-evaluates the HPD on every distinct vertex
@@ -28,6 +32,8 @@ import os
 import subprocess
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -108,6 +114,11 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-sample", type=int, default=2 ** 20)
     ap.add_argument("--ramp-steps", type=int, default=60, help="untimed steps before the W warm-up steps (clock ramp)")
     ap.add_argument("--backend", default="nccl", help="rehearsal only: 'gloo' runs the N>1 code path with ranks sharing one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks (other modes, CPU baseline, per-kernel times and rooflines, copy "
+                         "bandwidth, extra timing windows, step variants); a plain run only times the headline step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
     return ap.parse_args(argv)
 
 
@@ -188,6 +199,7 @@ def eager_step_fn(net, mode, xy, target, world, exchange=True):
     one = torch.ones((), device=xy.device)          # the seed of backward(): loss.backward() would fill a fresh one per step
     T = net._hash_table_size
     net.dp.persist_ok = True      # this loop lets go of every gradient at the top of each step (ops.PERSISTENT_TABLE_GRAD is opt-in)
+    last = {}                     # the last step's outputs (--dump-outputs)
 
     def step():
         for p in params:
@@ -201,7 +213,77 @@ def eager_step_fn(net, mode, xy, target, world, exchange=True):
         loss.backward(gradient=one)
         if world > 1 and exchange:
             parallel.allreduce_gradients(net, world)
+        last["rgb"], last["loss"] = rgb.detach(), loss.detach()
+    step.last = last
     return step
+
+
+def graphed_last_outputs(gs):
+    """rgb and loss of the LAST step of the most recent replay of a GraphedStep (static buffers of the variant it replayed)."""
+    st = next(iter(gs._graphs.values()))
+    pre = st.get("pre")
+    use = ("01" if pre[0] == 1 else "10") if ("W" in st and pre is not None) else "cold"    # replay_steady: "01" fills workspace 1
+    r = st["variants"][use][1][-1]
+    return {"rgb": r.out, "loss": r.loss}
+
+
+DUMP_FULL_MAX = 2 ** 16               # elements an array may have to be written in full whatever the others need
+DUMP_FIRST = {"rgb": 2 ** 22}         # ... and the step's own output, up to 16 MB: the gradients share what is left
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # what all arrays may take together, below the limit:
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_positions(numel, k):
+    """the fixed sample of k of numel flat positions (sorted) that --dump-outputs writes of a large array: seeded by numel alone"""
+    rng = np.random.default_rng(numel)
+    if numel <= 2 ** 24:
+        return np.sort(rng.choice(numel, k, replace=False))
+    return np.unique(rng.integers(0, numel, k))
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes arrays {name: tensor} as out_dir/<name>.npy in float32 (float64 stays float64).  Arrays of up to DUMP_FULL_MAX
+    elements (DUMP_FIRST: up to the number given there) are written in full; the larger ones share what is left of
+    DUMP_BUDGET_BYTES in proportion to their size, each
+    written in full if its share covers it, else as the values at dump_positions(numel, share) of its flattened form, so two
+    runs with the same arguments write the same positions."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    nbytes = {n: t.numel() * (8 if t.dtype == torch.float64 else 4) for n, t in arrays.items()}
+    large = [n for n, t in arrays.items() if t.numel() > DUMP_FIRST.get(n, DUMP_FULL_MAX)]
+    left = DUMP_BUDGET_BYTES - sum(b for n, b in nbytes.items() if n not in large)
+    frac = min(1.0, left / max(1, sum(nbytes[n] for n in large)))
+    host, total = {}, 0
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        k = int(flat.numel() * frac) if name in large else flat.numel()
+        if k < flat.numel():
+            flat = flat[torch.from_numpy(dump_positions(flat.numel(), k)).to(flat.device)]
+            a = flat.cpu().numpy()
+        else:
+            a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        host[name] = a
+        total += a.nbytes
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs, more than the {DUMP_LIMIT_BYTES} allowed")
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
+def step_outputs(net, last):
+    """What a caller of the timed step receives: the decoder output, the loss, and the gradient of every trainable parameter
+    (fp16 tables: the fp32 buffer it is accumulated in)."""
+    arrays = dict(last)
+    for name, p in net.named_parameters():
+        if not p.requires_grad:
+            continue
+        g = getattr(p, "grad_fp32", None)
+        g = p.grad if g is None else g
+        if g is not None:
+            arrays["grad." + name] = g
+    return arrays
 
 
 def timed(step, steps, warmup, world):
@@ -418,10 +500,11 @@ def main():
     results = {}
     broken = False
     in_graph_ms = None
-    hbm_copy = measure_hbm_copy_gbs(dev)          # this box's streaming-copy bandwidth, same run (fractions against it below)
+    # this box's streaming-copy bandwidth, same run (fractions against it below)
+    hbm_copy = measure_hbm_copy_gbs(dev) if a.full else None
     # the other modes are single-GPU side measurements: at N > 1 only the mode asked for runs (each mode would have to be collective-
     # matched across the ranks, a failure in any of them would cost the scaling line, and the driver computes scaling from `value`)
-    extra = [] if (a.no_extra_modes or world > 1) else [m for m in ("gngf_learning", "hash", "gngf_frozen", "cfg4_hash", "cfg5_hash_fp16")
+    extra = [] if (not a.full or a.no_extra_modes or world > 1) else [m for m in ("gngf_learning", "hash", "gngf_frozen", "cfg4_hash", "cfg5_hash_fp16")
                                                          if m != a.mode]
     kt, kcalls = {}, {}
     batches = {}
@@ -439,13 +522,12 @@ def main():
             learning = mode == "gngf_learning"
             # (the other single-kernel-chain modes: as many steps as the headline — 10 steps of 0.4 ms are a 4 ms window, ±1 % of noise)
             steps, warmup = (a.steps, a.warmup) if head else ((2, 1) if learning else (max(5, a.steps), max(2, a.warmup)))
-            if learning and head:
-                steps, warmup = min(a.steps, 5), min(a.warmup, 1)
             net, models = build_model(mode, dev, bounds)
             if world > 1:
                 parallel.enable_vertex_grid_exchange(net, world)
             loss_fn = train.Loss(delta=1, gamma=-2, epsilon=1)
             step = eager_step_fn(net, mode, xy, target, world)
+            last_outputs = step.last
             launch = "eager"
             unroll = 1
             if a.graph and not learning:
@@ -478,11 +560,13 @@ def main():
                     else:
                         step = gs.replay_steady
                         launch = "hipGraph" if unroll == 1 else f"hipGraph ({unroll} steps per replay)"
+                    last_outputs = None
                 except Exception as e:  # pragma: no cover
                     print(f"[bench] graph capture failed ({e!r}); running eagerly", file=sys.stderr)
                     if world > 1:
                         parallel.defer_vertex_stage(net, False)
                     step = eager_step_fn(net, mode, xy, target, world)
+                    last_outputs = step.last
             if not learning:
                 # Clock ramp: the chip reaches its steady matrix-core clock only after ~15 ms of sustained work (the same kernel
                 # is ~10 % slower before; tools/perf_decoder_warm.py), and W warm-up steps of 0.6 ms do not get there.  Untimed
@@ -491,6 +575,8 @@ def main():
                     step()
             per = unroll if (a.graph and not learning and launch.startswith("hipGraph (")) else 1
             dt = timed(step, steps // per, -(-warmup // per), world)       # exactly `steps` steps: steps / per replays of `per` steps each
+            if head and a.dump_outputs and rank == 0:
+                dump_outputs(a.dump_outputs, step_outputs(net, graphed_last_outputs(gs) if last_outputs is None else last_outputs))
             res = results[mode] = {"mpix_s": P * world * steps / dt / 1e6, "ms_per_step": dt / steps * 1e3, "steps": steps, "warmup": warmup,
                                    "launch": launch, "shape": {k: v for k, v in SHAPES[cfg_name].items()}}
             sc_ = getattr(net.dp, "step_config", None)
@@ -498,7 +584,7 @@ def main():
             res["step_chain"] = sc_.chain() if sc_ is not None else None
             if world > 1:
                 res["ms_per_step_per_rank"] = [t_ / steps * 1e3 for t_ in LAST_PER_RANK]
-            if not learning:
+            if a.full and not learning:
                 # the contract's window is `steps` steps (8 ms at the default K): five more windows of the same length, each bracketed
                 # like the first, show how much one window moves (every rank runs them: the barriers stay matched)
                 res["ms_per_step_windows"] = [timed(step, steps // per, 0, world) / steps * 1e3 for _ in range(5)]
@@ -507,16 +593,17 @@ def main():
             # not move those bytes, so its ratio exceeds 1 — it is printed as what it is, next to the hash modes' real fractions.
             sb_f, sb_b = survey_bytes(mode)
             sv = (sb_f + sb_b) * P * steps / dt / 1e9
-            res["roofline_survey"] = {"bytes_per_pixel": sb_f + sb_b, "achieved_GBs": sv, "frac_of_8TBs": sv / HBM_PEAK_GBS,
-                                      "frac_of_measured_copy": sv / hbm_copy}
-            if world > 1:
-                res["exchange"] = exchange_model(net, world, P)
-            else:
-                # the prediction a multi-GPU run of this mode is to be held against (weak scaling: the same 2^20 px per GPU)
-                res["exchange_model"] = {str(n): exchange_model(net, n, P) for n in (2, 4, 8)}
-                for em in res["exchange_model"].values():
-                    em["predicted_ms_per_step"] = res["ms_per_step"] + em["modelled_ring_allreduce_ms"]
-                    em["predicted_scaling_efficiency"] = res["ms_per_step"] / em["predicted_ms_per_step"]
+            if a.full:
+                res["roofline_survey"] = {"bytes_per_pixel": sb_f + sb_b, "achieved_GBs": sv, "frac_of_8TBs": sv / HBM_PEAK_GBS,
+                                          "frac_of_measured_copy": sv / hbm_copy}
+                if world > 1:
+                    res["exchange"] = exchange_model(net, world, P)
+                else:
+                    # the prediction a multi-GPU run of this mode is to be held against (weak scaling: the same 2^20 px per GPU)
+                    res["exchange_model"] = {str(n): exchange_model(net, n, P) for n in (2, 4, 8)}
+                    for em in res["exchange_model"].values():
+                        em["predicted_ms_per_step"] = res["ms_per_step"] + em["modelled_ring_allreduce_ms"]
+                        em["predicted_scaling_efficiency"] = res["ms_per_step"] / em["predicted_ms_per_step"]
             if SHAPES[cfg_name]["half"]:
                 res["table_gradient"] = "fp32 accumulation buffer handed over as param.grad_fp32 (ops.FP16_TABLE_GRAD_FP32), no fp16 .grad copy"
             if learning:
@@ -536,7 +623,7 @@ def main():
                 res["roofline"]["bf16_pipe"] = {"issued_tflop_per_step": issued / 1e12, "achieved": issued / (dt / steps) / 1e12, "peak": 2500.0,
                                                 "unit": "TFLOP/s", "frac": issued / (dt / steps) / 1e12 / 2500.0,
                                                 "products_per_fp32_product": {"logits": 6, "dW_dh": nprod_bwd}}
-            if head and launch.startswith("hipGraph"):
+            if a.full and head and launch.startswith("hipGraph"):
                 # decoder_bwd's duration INSIDE the replayed graph, from the device clock the kernel stamps (events cannot be
                 # recorded in a replayed hipGraph here): one sample per burst of replays.  Every rank runs it: at world > 1 a step
                 # carries the gradient exchange, and collectives must stay matched across ranks.
@@ -556,7 +643,7 @@ def main():
                 except Exception as e:  # pragma: no cover
                     in_graph_ms = None
                     print(f"[bench] in-graph span unavailable ({e!r})", file=sys.stderr)
-            if head and world == 1 and a.graph and not learning:
+            if a.full and head and world == 1 and a.graph and not learning:
                 # the same step with the optimizer in the graph (get_optimizer's Adam as one launch): reported, not the metric
                 try:
                     opt = train.get_optimizer(net, 1e-2, 1e-3, 1e-3, 0.0, 0.0, 1e-6)
@@ -567,7 +654,7 @@ def main():
                     del opt, gso
                 except Exception as e:  # pragma: no cover
                     res["with_adam_ms_per_step"] = repr(e)
-            if world == 1 and a.graph and not learning and a.full_outputs:
+            if a.full and world == 1 and a.graph and not learning and a.full_outputs:
                 # the same step returning the reference's index tensor as well ((P,L,4[,K]) int64, models.py:475-484): the metric's
                 # step turns it off (net.return_indices = False, build_model) — its cost is reported here, never in `value`
                 try:
@@ -585,7 +672,7 @@ def main():
                     res["with_full_outputs_ms_per_step"] = repr(e)
                 finally:
                     net.return_indices = False
-            if (head and not learning) or (learning and world == 1):
+            if a.full and ((head and not learning) or (learning and world == 1)):
                 # per-kernel launch times inside eagerly launched steps (the `roofline` objects).  At N > 1 EVERY rank runs them — the
                 # eager step holds the gradient exchange, and collectives must stay matched — and rank 0 reports its own.
                 try:
@@ -726,7 +813,7 @@ def main():
             # same kernel, timed by its own device-clock stamps inside the replayed graph (agrees with rocprofv3's average)
             roof["in_graph_launch_ms"] = in_graph_ms
             roof["in_graph_frac"] = roof["algorithmic_flops_per_pixel"] * P / (in_graph_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.mode, a.cpu_sample)
         assert line["n_gpus"] == a.gpus
         print(json.dumps(line))

@@ -14,6 +14,8 @@ Golden groups follow SURVEY.md §8c:
   G7 end_to_end            models.py:394-484 + utils.py:91-174 + functions.py:96-127,243-281
   G8 train_curve           functions.py:139-355 (optional, slow)
   G9 decoder mlp           models.py:382-392,469-470
+  G18 params settings      params.py (values only)
+  G19 driver epoch         functions.py:139-355,761-781 on the reference's classes (tests/test_reference_driver_cpu.py)
 """
 import argparse
 import os
@@ -794,7 +796,34 @@ def g12s(F_, U_, M, P_):
          ref_fp32_vs_fp64_rgb_abs=np.float64(own_rgb), fp64_topk_probs=exact_tp, fp64_topk_idx=exact_idx)
 
 
-GROUPS = {"G12s": g12s, "G17": g17, "G15": g15, "G16": g16, "G3b": g3b, "G11": g11, "G12": g12, "G13": g13, "G14": g14, "G10": g10, "G1": g1, "G2": g2_g3, "G4": g4, "G5": g5, "G6": g6, "G7": g7, "G9": g9}
+def g18(F_, U_, M, P_):
+    """the reference's settings (params.py: its plain values, no code) for the tests that need its `params` module"""
+    import json
+    settings = {k: v for k, v in vars(P_).items()
+                if not k.startswith("_") and isinstance(v, (bool, int, float, str, list, dict, type(None)))}
+    path = os.path.join(OUT, "G18_reference_params.json")
+    with open(path, "w") as f:
+        json.dump({"source": "params.py of the reference, values only", "settings": settings}, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote", path)
+
+
+def g19(F_, U_, M, P_):
+    """the reference's driver (functions.train_step + the checkpoint block) on its own classes, one epoch per indexing mode, as
+    tests/test_reference_driver_cpu.py runs it live: initial weights, epoch results, parameters after the three steps"""
+    import subprocess
+    import tempfile
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import test_reference_driver_cpu as drv
+    for mode in ("gngf", "hash"):
+        path = os.path.join(OUT, f"G19_reference_driver_{mode}.npz")
+        with tempfile.TemporaryDirectory() as d:
+            r = drv.run_driver(mode, d, ref=rh.REF_ROOT, record=path)
+        assert r.returncode == 0, r.stderr[-3000:]
+        print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
+GROUPS = {"G12s": g12s, "G17": g17, "G15": g15, "G16": g16, "G3b": g3b, "G11": g11, "G12": g12, "G13": g13, "G14": g14, "G10": g10, "G1": g1, "G2": g2_g3, "G4": g4, "G5": g5, "G6": g6, "G7": g7, "G9": g9, "G18": g18, "G19": g19}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()

@@ -163,7 +163,7 @@ def test_bench_with_two_ranks_runs_as_a_fresh_process(mode, tmp_path):
     # levels and take the level-interleaved kernels instead of the generic ones the 4-GPU config runs)
     pixels = 2 ** 20 if mode == "cfg4_hash" else 2 ** 18
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4", "--warmup", "1",
-           "--no-cpu-baseline", "--mode", mode, "--pixels", str(pixels), "--ramp-steps", "2"]
+           "--full", "--no-cpu-baseline", "--mode", mode, "--pixels", str(pixels), "--ramp-steps", "2"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=840, cwd=root)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -1,6 +1,6 @@
-"""CPU (build container only): the REFERENCE'S OWN DRIVER runs against the drop-in boundary.
+"""CPU: the REFERENCE'S OWN DRIVER runs against the drop-in boundary (live, or against its recorded results: see below).
 
-`/root/reference/functions.py` (imported untouched, as oracle/ref_harness.py does) is given the classes of
+The reference's `functions.py` (imported untouched, as oracle/ref_harness.py does) is given the classes of
 `collision_handling_in_instantngp_amd/reference_shim/models.py` under the name `models`, and its `train_step`
 (functions.py:139-355) plus the checkpoint block (functions.py:761-781) are driven for one epoch in both indexing modes.
 There is no GPU here, and the product has no CPU path — so, IN THIS TEST ONLY, the handful of `ops` entry points the module
@@ -14,7 +14,11 @@ oracle; the product never sees them).  What this pins is the CALL CONTRACT that 
     reference itself as here (AttributeError at functions.py:775 on both sides);
   * the numbers: the epoch's loss, MSE, reconstructed image and parameters after the three optimizer steps equal those of the
     reference's own classes from the same initial weights.
-The reference's files stay in /root/reference; nothing of them is copied."""
+Unless GNGF_REFERENCE_ROOT names the reference's directory, the same classes are driven by the product's own
+`train.train_step` / `train.get_optimizer` / `train.Loss` (the reference's signatures) with the reference's settings
+(tests/golden/G18_reference_params.json) and held to what the reference's driver and classes computed in the live run
+(tests/golden/G19_reference_driver_<mode>.npz, written by `python oracle/make_goldens.py --only G18,G19`).
+Nothing of the reference's files is copied: the fixtures hold settings and results only."""
 import os
 import subprocess
 import sys
@@ -24,7 +28,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "collision_handling_in_instantngp_amd", "reference_shim")
-REF = os.environ.get("GNGF_REFERENCE_ROOT", "/root/reference")
+REF = os.environ.get("GNGF_REFERENCE_ROOT", "")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 SCRIPT = textwrap.dedent(r'''
     import importlib, os, sys, types
@@ -32,33 +37,48 @@ SCRIPT = textwrap.dedent(r'''
     import torch
     import matplotlib
     matplotlib.use("Agg")
-    MODE, SHIM, ROOT, REF = sys.argv[1:5]
+    MODE, SHIM, ROOT, REF, GOLDEN = sys.argv[1:6]
+    RECORD = sys.argv[6] if len(sys.argv) > 6 else None      # live run only: write the reference's side to this .npz
     hash_mode = MODE == "hash"
-    for name in ("cv2", "wandb"):
-        sys.modules[name] = types.ModuleType(name)
-    tv = types.ModuleType("torchvision"); tv.io = types.ModuleType("torchvision.io"); tv.transforms = types.ModuleType("torchvision.transforms")
-    sys.modules.update({"torchvision": tv, "torchvision.io": tv.io, "torchvision.transforms": tv.transforms})
-    sys.path[:0] = [ROOT, REF]
-    real = torch.set_default_device
-    torch.set_default_device = lambda *a, **k: None            # functions.py:52 asks for 'cuda'
-    try:
-        functions = importlib.import_module("functions")      # the reference's, untouched
-        utils = importlib.import_module("utils")
-        params = importlib.import_module("params")
-        ref_models = importlib.import_module("models")        # the reference's own classes: the numbers to match
-    finally:
-        torch.set_default_device = real
-    cpu = torch.device("cpu")
-    for m_ in (functions, utils, ref_models):
-        m_.device = cpu
-        m_.should_use_hash_function = hash_mode
+    LIVE = bool(REF) and os.path.isfile(os.path.join(REF, "functions.py"))
+    sys.path[:0] = [ROOT]
+    if LIVE:
+        for name in ("cv2", "wandb"):
+            sys.modules[name] = types.ModuleType(name)
+        tv = types.ModuleType("torchvision"); tv.io = types.ModuleType("torchvision.io"); tv.transforms = types.ModuleType("torchvision.transforms")
+        sys.modules.update({"torchvision": tv, "torchvision.io": tv.io, "torchvision.transforms": tv.transforms})
+        sys.path[:0] = [REF]
+        real = torch.set_default_device
+        torch.set_default_device = lambda *a, **k: None            # functions.py:52 asks for 'cuda'
+        try:
+            functions = importlib.import_module("functions")      # the reference's, untouched
+            utils = importlib.import_module("utils")
+            params = importlib.import_module("params")
+            ref_models = importlib.import_module("models")        # the reference's own classes: the numbers to match
+        finally:
+            torch.set_default_device = real
+        cpu = torch.device("cpu")
+        for m_ in (functions, utils, ref_models):
+            m_.device = cpu
+            m_.should_use_hash_function = hash_mode
+        del sys.modules["models"]
+    else:
+        # no reference: its settings (tests/golden/G18_reference_params.json) as the `params` module, and the product's own
+        # restatement of the driver (train.get_optimizer / train.Loss / train.train_step, same signatures) against what the
+        # reference's driver and classes computed in the live run (tests/golden/G19_reference_driver_<mode>.npz)
+        import json
+        params = types.ModuleType("params")
+        with open(os.path.join(GOLDEN, "G18_reference_params.json")) as f:
+            params.__dict__.update(json.load(f)["settings"])
+        sys.modules["params"] = params
     params.should_use_hash_function = hash_mode
     # ... and the replacement, under its own module name (the shim reads `params` of the caller at call time)
-    del sys.modules["models"]
     sys.path.insert(0, SHIM)
     shim = importlib.import_module("models")
     assert shim.__file__.startswith(SHIM), shim.__file__
-    from collision_handling_in_instantngp_amd import models as hip_models, ops
+    from collision_handling_in_instantngp_amd import models as hip_models, ops, train as hip_train
+    if not LIVE:
+        functions = utils = hip_train
 
     # ------------------------------------------------------------------ plain-torch stand-ins for the HIP entry points (TEST ONLY)
     def cells(xy, n_ls):
@@ -144,8 +164,8 @@ SCRIPT = textwrap.dedent(r'''
     ops.mse_loss = lambda pred, label: torch.nn.functional.mse_loss(pred, label)
     ops.slot_order = lambda *a, **k: None
 
-    # ------------------------------------------------------------------ the reference's driver, twice
-    img = np.load(os.path.join(ROOT, "tests", "golden", "strawberry_rgb.npz"))["img"][100:136, 60:108]     # a 36 x 48 crop
+    # ------------------------------------------------------------------ the reference's driver (or the product's restatement of it)
+    img = np.load(os.path.join(GOLDEN, "strawberry_rgb.npz"))["img"][100:136, 60:108]     # a 36 x 48 crop
     h, w = img.shape[:2]
     rows, cols = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
     X = torch.tensor(np.stack([rows, cols], -1).reshape(-1, 2)).float() / (max(w, h) - 1)        # utils.py:56-59, main.py:50-51
@@ -179,49 +199,82 @@ SCRIPT = textwrap.dedent(r'''
             saved["HPD"] = "AttributeError"
         return net, out, saved
 
-    init_net = ref_models.GeneralNeuralGaugeFields(**kw)
-    init = {k: v.clone() for k, v in init_net.state_dict().items()}
-    ref_net, ref_out, ref_saved = run(ref_models.GeneralNeuralGaugeFields, init)
+    if LIVE:
+        init_net = ref_models.GeneralNeuralGaugeFields(**kw)
+        init = {k: v.clone() for k, v in init_net.state_dict().items()}
+        ref_net, ref_out, ref_saved = run(ref_models.GeneralNeuralGaugeFields, init)
+        # what the checks below read of the reference's side (recorded by RECORD, read back when the reference is absent)
+        ref = {"loss": ref_out[0], "mse": ref_out[5], "image": ref_out[1], "kls": ref_out[6], "kls2": ref_out[7],
+               "coll_shape": tuple(ref_out[2].shape), "min_coll_shape": tuple(ref_out[3].shape), "n_out": len(ref_out),
+               "hpd": ref_saved["HPD"] if isinstance(ref_saved["HPD"], str) else sorted(ref_saved["HPD"]),
+               "keys": {part: list(ref_saved[part]) for part in ("whole", "encoding", "mlp")},
+               "whole": {k: v.clone() for k, v in ref_saved["whole"].items()},
+               "opt_lr": [g["lr"] for g in ref_saved["opt"]["param_groups"]],
+               "opt_n": [len(g["params"]) for g in ref_saved["opt"]["param_groups"]]}
+        if RECORD:
+            import json
+            meta = {k: ref[k] for k in ("loss", "mse", "coll_shape", "min_coll_shape", "n_out", "hpd", "keys", "opt_lr", "opt_n")}
+            meta["init_keys"] = list(init)
+            arrays = {"image": ref["image"], "meta": np.array(json.dumps(meta))}
+            arrays.update({"init/" + k: v.numpy() for k, v in init.items()})
+            arrays.update({"after/" + k: v.numpy() for k, v in ref["whole"].items()})
+            for k in ("kls", "kls2"):
+                if ref[k] is not None:
+                    arrays[k] = np.asarray(ref[k])
+            np.savez_compressed(RECORD, **arrays)
+    else:
+        import json
+        rec = np.load(os.path.join(GOLDEN, f"G19_reference_driver_{MODE}.npz"), allow_pickle=False)
+        meta = json.loads(str(rec["meta"]))
+        init = {k: torch.from_numpy(rec["init/" + k]) for k in meta["init_keys"]}
+        ref = dict(meta, image=rec["image"], kls=(rec["kls"] if "kls" in rec.files else None),
+                   kls2=(rec["kls2"] if "kls2" in rec.files else None),
+                   coll_shape=tuple(meta["coll_shape"]), min_coll_shape=tuple(meta["min_coll_shape"]),
+                   whole={k: torch.from_numpy(rec["after/" + k]) for k in meta["keys"]["whole"]})
     our_net, our_out, our_saved = run(shim.GeneralNeuralGaugeFields, init)
     assert isinstance(our_net, hip_models.GeneralNeuralGaugeFields)
 
     names = ["loss", "image", "collisions", "min_possible_collisions", "counts_per_level", "mse", "kl_div_losses", "collisions_losses", "indices_per_level"]
-    assert len(ref_out) == len(our_out) == 9
-    np.testing.assert_allclose(our_out[0], ref_out[0], rtol=2e-5, err_msg="loss of the epoch")
-    np.testing.assert_allclose(our_out[5], ref_out[5], rtol=2e-5, err_msg="mse of the epoch")
-    assert our_out[1].shape == ref_out[1].shape == (h, w, 3) and our_out[1].dtype == ref_out[1].dtype
-    assert np.abs(our_out[1].astype(np.int64) - ref_out[1].astype(np.int64)).max() <= 1, "reconstructed image (int, 0..255)"
+    assert ref["n_out"] == len(our_out) == 9
+    np.testing.assert_allclose(our_out[0], ref["loss"], rtol=2e-5, err_msg="loss of the epoch")
+    np.testing.assert_allclose(our_out[5], ref["mse"], rtol=2e-5, err_msg="mse of the epoch")
+    assert our_out[1].shape == ref["image"].shape == (h, w, 3) and our_out[1].dtype == ref["image"].dtype
+    assert np.abs(our_out[1].astype(np.int64) - ref["image"].astype(np.int64)).max() <= 1, "reconstructed image (int, 0..255)"
     if hash_mode:
-        assert our_out[6] is None and our_out[7] is None and ref_out[6] is None
-        assert our_saved["HPD"] == ref_saved["HPD"] == "AttributeError"          # functions.py:775 fails in the reference itself in hash mode
+        assert our_out[6] is None and our_out[7] is None and ref["kls"] is None
+        assert our_saved["HPD"] == ref["hpd"] == "AttributeError"          # functions.py:775 fails in the reference itself in hash mode
     else:
-        np.testing.assert_allclose(our_out[6], ref_out[6], rtol=2e-4, atol=1e-7, err_msg="JS/KL terms of the epoch")
-        assert sorted(our_saved["HPD"]) == sorted(ref_saved["HPD"])
+        np.testing.assert_allclose(our_out[6], ref["kls"], rtol=2e-4, atol=1e-7, err_msg="JS/KL terms of the epoch")
+        assert sorted(our_saved["HPD"]) == ref["hpd"]
     # collisions: computed from the torch.empty buffer (partly uninitialised in both): contract = type and shape only
-    assert tuple(our_out[2].shape) == tuple(ref_out[2].shape) and tuple(our_out[3].shape) == tuple(ref_out[3].shape)
+    assert tuple(our_out[2].shape) == ref["coll_shape"] and tuple(our_out[3].shape) == ref["min_coll_shape"]
     for part in ("whole", "encoding", "mlp"):
-        assert list(our_saved[part]) == list(ref_saved[part]), part                # same keys, same order
-    for k, v in ref_saved["whole"].items():
+        assert list(our_saved[part]) == ref["keys"][part], part                # same keys, same order
+    for k, v in ref["whole"].items():
         got = our_saved["whole"][k]
         assert got.shape == v.shape and got.dtype == v.dtype, k
         if v.dtype.is_floating_point:
             scale = float(v.abs().max()) + 1e-12
             assert float((got - v).abs().max()) <= 2e-3 * scale, (k, float((got - v).abs().max()), scale)   # three Adam steps (eps 1e-15)
-    assert [g["lr"] for g in our_saved["opt"]["param_groups"]] == [g["lr"] for g in ref_saved["opt"]["param_groups"]]
-    assert [len(g["params"]) for g in our_saved["opt"]["param_groups"]] == [len(g["params"]) for g in ref_saved["opt"]["param_groups"]]
-    print("DRIVER OK", MODE)
+    assert [g["lr"] for g in our_saved["opt"]["param_groups"]] == ref["opt_lr"]
+    assert [len(g["params"]) for g in our_saved["opt"]["param_groups"]] == ref["opt_n"]
+    print("DRIVER OK", MODE, "live" if LIVE else "recorded")
 ''')
+
+
+def run_driver(mode, work_dir, ref=REF, record=None):
+    """runs SCRIPT in a fresh interpreter; `ref`: the reference's directory ("" = recorded results); `record`: .npz to write"""
+    script = os.path.join(str(work_dir), "drive.py")
+    with open(script, "w") as f:
+        f.write(SCRIPT)
+    env = dict(os.environ)
+    env.pop("PYTHONPATH", None)
+    return subprocess.run([sys.executable, script, mode, SHIM, ROOT, ref, GOLDEN] + ([record] if record else []), env=env,
+                          capture_output=True, text=True, timeout=580, cwd=str(work_dir))
 
 
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("mode", ["gngf", "hash"])
 def test_reference_train_step_and_checkpoint_block_run_against_the_boundary(tmp_path, mode):
-    if not os.path.isfile(os.path.join(REF, "functions.py")):
-        pytest.skip("reference not present (GPU box): this rehearsal runs in the build container only")
-    script = tmp_path / "drive.py"
-    script.write_text(SCRIPT)
-    env = dict(os.environ)
-    env.pop("PYTHONPATH", None)
-    r = subprocess.run([sys.executable, str(script), mode, SHIM, ROOT, REF], env=env, capture_output=True, text=True, timeout=580,
-                       cwd=str(tmp_path))
+    r = run_driver(mode, tmp_path)
     assert r.returncode == 0 and f"DRIVER OK {mode}" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])

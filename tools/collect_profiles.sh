@@ -1,8 +1,8 @@
 #!/bin/bash
-# gpurun_out/prof_<tag>_* (tools/profile_round.sh) -> profiles/<tag>_*  (summaries only; run in the build container after the gpurun call)
+# $OUT/prof_<tag>_* (tools/profile_round.sh; default out/) -> profiles/<tag>_*  (summaries only; run on the host after the profiling run)
 set -eu
 TAG=${1:-r05}
-O=gpurun_out
+O=${OUT:-out}
 for pair in frozen:gngf_frozen hash:hash learning:gngf_learning cfg4:cfg4_hash cfg5:cfg5_hash_fp16; do
   d=${pair%%:*}; m=${pair##*:}
   python tools/prof_summary.py $O/prof_${TAG}_$d 30 > profiles/${TAG}_kernel_stats_$m.txt
