@@ -136,6 +136,7 @@ def table_view(owner):
 
 
 STEP_TRACE = None            # tests: a list that receives one (what, {facts}) record per dispatch decision of a backward pass
+#                              (and one "hpd_chunk" record per row chunk of each HpdVertexFunction pass)
 SEEN_STEP_CONFIGS = None     # tests: a set that receives StepConfig.chain() of every forward pass (tests/conftest.py records it per test)
 
 
@@ -645,6 +646,7 @@ class HpdVertexFunction(torch.autograd.Function):
                 else:
                     call("gngf_logits_topk_pbar", ptr(z), ptr(tv[u0:u0 + n]), ptr(ti[u0:u0 + n]), ptr(rowstat[u0:u0 + n]),
                          ptr(mw[u0:u0 + n] if pbar is not None else None), L if pbar is not None else 0, ptr(pbar), n, T, K, stream_ptr())
+            _trace("hpd_chunk", pass_="fwd", u0=u0, n=n, epi=epi, kept=u0 in zcache, fused=False, pipelined=pipelined)
             if pipelined:
                 ready = torch.cuda.Event()
                 ready.record(main)
@@ -722,6 +724,7 @@ class HpdVertexFunction(torch.autograd.Function):
             HpdVertexFunction._hidden_backward(hs_all, dH, params, grads, n_layers)
             return (None, None, None, None, None, None, None, *grads)
         prep_serial = None
+        Lq, Kq = (L if g_pbar is not None else 0), (K if g_tv is not None else 0)
         for u0 in range(0, NV, rows):
             n = min(rows, NV - u0)
             hs = [h[u0:u0 + n] for h in hs_all]
@@ -731,14 +734,15 @@ class HpdVertexFunction(torch.autograd.Function):
                 if dz_buf is None:
                     dz_buf = torch.empty((min(rows, NV), T), dtype=_f32, device=dev)
                 dz = dz_buf[:n]
+            fused = (lowrank and TUNING.hpd_bwd_fused and TUNING.hpd_gemm_split_bf16
+                     and query("gngf_hpd_bwd_fused_applies", n, T, Lq, Kq, W_last.shape[1]) == 1)
+            _trace("hpd_chunk", pass_="bwd", u0=u0, n=n, epi=False, kept=have_z, fused=fused, pipelined=False)
             if lowrank:
                 # logits (again, unless kept), then softmax / top-K / batch-mean backward in place; db of the last layer is fused in
                 if not have_z:
                     with _split_gemm():
                         call("gngf_linear_fwd", ptr(hs[-1]), ptr(W_last), ptr(b_last), ptr(dz), n, T, W_last.shape[1], ACT_NONE, stream_ptr())
-                Lq, Kq = (L if g_pbar is not None else 0), (K if g_tv is not None else 0)
-                if (TUNING.hpd_bwd_fused and TUNING.hpd_gemm_split_bf16
-                        and query("gngf_hpd_bwd_fused_applies", n, T, Lq, Kq, W_last.shape[1]) == 1):
+                if fused:
                     if prep_serial is None:
                         prep_serial = _HpdBwdPlanes(hs_all[-1], mw, W_last, g_pbar, Lq, 2 if TUNING.hpd_bwd_two_planes else 3)
                     dotv = scratch[:n]
@@ -802,7 +806,9 @@ class HpdVertexFunction(torch.autograd.Function):
         def fused(n):
             return (TUNING.hpd_bwd_fused and TUNING.hpd_gemm_split_bf16
                     and query("gngf_hpd_bwd_fused_applies", n, T, Lq, Kq, W_last.shape[1]) == 1)
-        prep = (_HpdBwdPlanes(hs_all[-1], mw, W_last, g_pbar, Lq, planes) if fused(min(rows, NV)) else None)
+        # the whole chunks and the ragged last one differ in size: either of them may be the fused one
+        sizes = {min(rows, NV - u0) for u0 in range(0, NV, rows)}
+        prep = (_HpdBwdPlanes(hs_all[-1], mw, W_last, g_pbar, Lq, planes) if any(fused(n) for n in sizes) else None)
 
         def stage_b(dz, n, u0):
             if fused(n):          # one read of the logits: the row dots only
@@ -830,6 +836,7 @@ class HpdVertexFunction(torch.autograd.Function):
             n = min(rows, NV - u0)
             hs = [h[u0:u0 + n] for h in hs_all]
             dz = zcache.pop(u0, None)
+            _trace("hpd_chunk", pass_="bwd", u0=u0, n=n, epi=False, kept=dz is not None, fused=fused(n), pipelined=True)
             if dz is None:                                     # A: not kept by the forward
                 dz = dz_bufs[n_unkept % len(dz_bufs)][:n]
                 n_unkept += 1
