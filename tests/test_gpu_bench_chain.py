@@ -207,7 +207,9 @@ def test_model_gradients_when_the_generic_pixel_stage_runs(mode, interleaved_off
     C side an UNINITIALISED fp32 vertex grid next to the fixed-point one whenever the level-interleaved kernel did not apply —
     the 4096^2 shape (297 KB image), or any shape after gngf_set_tiled_interleaved(0) — and the generic kernels accumulated
     into it.  Now the launcher's own decision (gngf_tiled_interleaved_applies) picks the buffers.  The allocator is poisoned with
-    NaN first; the table gradient of the tiled dispatch must equal the direct form's (float atomics: fp32 round-off)."""
+    NaN first; the table gradient of the tiled dispatch must equal the direct form's (float atomics: fp32 round-off), and, for the
+    vertex-table source, every row of it must match the float64 oracle on the step's own d enc within the error model of
+    tests/test_gpu_step_config_matrix.py (entries no term reaches: exactly zero)."""
     import bench
     from collision_handling_in_instantngp_amd import models, ops, _lib
     shape = "cfg2" if interleaved_off else "cfg4"
@@ -231,17 +233,25 @@ def test_model_gradients_when_the_generic_pixel_stage_runs(mode, interleaved_off
             net.compute_pbar = False
         with torch.no_grad():
             net.encoding.packed_tables().mul_(100.0)
-        grads = {}
+        grads, captured = {}, []
+        real_decoder_apply = ops.decoder_apply
+
+        def spy(enc, *a, **kw):
+            enc.register_hook(lambda g: captured.append(g.detach().clone()))
+            return real_decoder_apply(enc, *a, **kw)
         for path in ("tiled", "direct"):
             net.zero_grad()
             ops.ENCODE_PATH = path
             _poison_allocator()
+            if path == "tiled":
+                ops.decoder_apply = spy            # the d enc of the tiled step, for the oracle
             try:
                 with net.fused_mse(target, gloss=1.0):
                     rgb, _p, _i, _c = net(xy, 1.0)
                 ops.mse_loss(rgb, target).backward()
             finally:
                 ops.ENCODE_PATH = "auto"
+                ops.decoder_apply = real_decoder_apply
             torch.cuda.synchronize()
             grads[path] = torch.stack([net.encoding._hash_tables[l].weight.grad for l in range(L)]).clone()
         assert len(trace) == 1 and not trace[0]["interleaved"] and not trace[0]["dG64"] and trace[0]["bound"], trace
@@ -252,8 +262,18 @@ def test_model_gradients_when_the_generic_pixel_stage_runs(mode, interleaved_off
         assert mx > 0
         # (vertex-table source with a freshly initialised HPD: a million entries meet in a few dozen rows, and the DIRECT form
         # adds them one float atomic at a time — its own fp32 accumulation error is what the looser bound covers)
+        # (that bound only guards against gross faults; the row-by-row check against the oracle below holds the chain)
         tol = 2e-5 if mode == "hash" else 5e-3
         parity_close(gt, gd, 1e-3, tol * mx, f"{shape} {mode} interleaved_off={interleaved_off}: model table gradient, tiled (generic kernels) vs direct form")
+        if mode == "gngf_frozen":
+            from test_gpu_step_config_matrix import check_rows_against_oracle, staged_sink
+            assert len(captured) == 1, len(captured)
+            _tv, ti, w, vstride, _NV, _order = net._frozen_vertex_table(ops.BLEND_CODES[True])
+            n_ls = np.array(net._n_ls_host, np.int32)
+            chunk = ops.EncodePlan(P, [int(n) for n in n_ls], F).chunk
+            check_rows_against_oracle(f"{shape} {mode} interleaved_off={interleaved_off} (generic pixel stage)", gt, xy,
+                                      np.ascontiguousarray(captured[0].float().cpu().numpy()), n_ls, T, F, trace[0]["Ls"],
+                                      staged_sink(trace, "vertex_table"), "vertex_table", chunk, ti, w, vstride)
     finally:
         ops.PIXEL_BWD_TRACE = prev_trace
         _lib.query("gngf_set_tiled_interleaved", prev_il)
