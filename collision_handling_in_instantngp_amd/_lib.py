@@ -53,7 +53,6 @@ SIGNATURES = {
     "gngf_decoder_bwd_slabs": [_L],
     "gngf_decoder_slab_floats": [_I, _I],
     "gngf_set_gemm_split_bf16": [_I],
-    "gngf_set_decoder_split_bf16": [_I],
     "gngf_set_decoder_bwd_hybrid": [_I],
     "gngf_linear_fwd": [_P, _P, _P, _P, _L, _I, _I, _I, _P],
     "gngf_linear_bwd_input": [_P, _P, _P, _P, _L, _I, _I, _I, _P],
@@ -92,7 +91,7 @@ SIGNATURES = {
     "gngf_adam_step": [_P, _I, _L, _P, _P, _P, _I, _F, _F, _F, _F, _P],
 }
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class BinJob(ctypes.Structure):

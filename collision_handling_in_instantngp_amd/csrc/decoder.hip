@@ -98,11 +98,6 @@ template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
 #define MFMA_VV_ZERO(acc, a, b) asm("v_mfma_f32_32x32x2_f32 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b))
 #define MFMA_DRAIN(x, y) asm volatile("s_nop 15\n\ts_nop 2" : "+v"(x), "+v"(y))
 #define MFMA_DRAIN1(x) asm volatile("s_nop 15\n\ts_nop 2" : "+v"(x))
-// scheduling groups (LLVM SchedGroupMask): the next N instructions of that class, in the order the groups are written
-#define SG_MFMA(n) __builtin_amdgcn_sched_group_barrier(0x008, (n), 0)
-#define SG_VALU(n) __builtin_amdgcn_sched_group_barrier(0x002, (n), 0)
-#define SG_DSR(n) __builtin_amdgcn_sched_group_barrier(0x100, (n), 0)
-#define SG_DSW(n) __builtin_amdgcn_sched_group_barrier(0x200, (n), 0)
 
 // Coalesced copy of the raw weights into LDS with a +1 padded row stride (conflict-free strided reads afterwards):
 //   W0s [64][in_dim+1] | W1s [64][65] | W2s [4][65] | b0 [64] | b1 [64] | b2 [4]
@@ -409,10 +404,9 @@ template <int KIN> struct BwdLds {
 // instead of 96 of 64, and the splitting issues underneath them.  The weight-gradient products (pixel on the k axis, fp32
 // transposition images) stay on the fp32 pipe, which keeps the kernel below the power limit of an all-bf16 one.
 // TRAIN (with HYB): forward AND backward of the decoder for the training step whose loss is MSELoss(rgb, target) with a KNOWN
-// upstream gradient (gloss): the tile's hidden layers are computed here (both layers on the bf16 pipe with the exact split, as
-// decoder_fwd_split_kernel), rgb is WRITTEN to Yout, d rgb is formed from it and the target, and the backward phases follow on
-// the registers that hold h1 / h2 — the hidden layers never travel through HBM (1 GB per step at 2^20 pixels) and the forward
-// kernel's launch disappears.
+// upstream gradient (gloss): the tile's hidden layers are computed here (both layers on the bf16 pipe with the exact split),
+// rgb is WRITTEN to Yout, d rgb is formed from it and the target, and the backward phases follow on the registers that hold
+// h1 / h2 — the hidden layers never travel through HBM (1 GB per step at 2^20 pixels) and the forward kernel's launch disappears.
 template <int KIN, bool LEAKY, bool EXACT, bool RECOMPUTE, bool HYB = false, bool TRAIN = false>
 __global__ void __launch_bounds__(kDecThreads, 1)
 decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, const float* __restrict__ dY,
@@ -1318,33 +1312,16 @@ static size_t bwd_smem_bytes_hybrid(int out_dim) {
 // bf16 pipe with the exact three-way split, weight gradients on the fp32 pipe); 0: all products on the fp32 pipe
 static int g_decoder_bwd_hybrid = 1;
 
-// 1: in_dim 32 / 64 run on the split-bf16 kernels (decoder_split.inc); 0: everything on the fp32 matrix pipe
-static int g_decoder_split = 0;
-
 }  // namespace gngf
 
 using namespace gngf;
 
-// Switches the decoder between the fp32-MFMA kernels and the split-bf16 ones (same results to fp32 rounding); returns the
-// previous setting.  With the split kernels the hidden-layer buffer is neither written nor read.
-// Returns -1 (and changes nothing) when the library was built without them (the default: make SPLIT=1 builds them).
-extern "C" int gngf_set_decoder_split_bf16(int on) {
-#if defined(GNGF_DECODER_SPLIT_KERNELS)
-  const int prev = g_decoder_split;
-  g_decoder_split = on ? 1 : 0;
-  return prev;
-#else
-  (void)on;
-  return -1;
-#endif
-}
 // Switch for the hybrid backward kernel (see g_decoder_bwd_hybrid); returns the previous setting.
 extern "C" int gngf_set_decoder_bwd_hybrid(int on) {
   const int prev = g_decoder_bwd_hybrid;
   g_decoder_bwd_hybrid = on ? 1 : 0;
   return prev;
 }
-static bool decoder_split_applies(int in_dim) { return g_decoder_split && in_dim == 32; }
 
 #define DISPATCH_KIN(in_dim, ...)                                         \
   if ((in_dim) <= 16) { constexpr int kKIN = 16; __VA_ARGS__; }           \
@@ -1372,21 +1349,6 @@ extern "C" int gngf_decoder_fwd(const float* enc, const float* W0, const float* 
   const int64_t tiles = (P + 127) / 128;
   const unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);       // one persistent workgroup per CU
   const size_t smem = sizeof(float) * (size_t)raw_offsets(in_dim).total;
-#if defined(GNGF_DECODER_SPLIT_KERNELS)
-  if (decoder_split_applies(in_dim)) {
-    hipStream_t s = as_stream(stream);
-    const unsigned grid = (unsigned)(tiles < 512 ? tiles : 512);     // two persistent workgroups per CU
-    const size_t smem = sizeof(float) * (size_t)((in_dim == 32 ? SplitFwd<32>::kFragWords : SplitFwd<64>::kFragWords) + SplitFwd<32>::kBiasWords + raw_offsets(in_dim).total);
-    if (in_dim == 32) {
-      if (leaky) decoder_fwd_split_kernel<32, true><<<dim3(grid), dim3(kDecThreads), smem, s>>>(enc, W0, b0, W1, b1, W2, b2, rgb, P, out_dim);
-      else decoder_fwd_split_kernel<32, false><<<dim3(grid), dim3(kDecThreads), smem, s>>>(enc, W0, b0, W1, b1, W2, b2, rgb, P, out_dim);
-    } else {
-      if (leaky) decoder_fwd_split_kernel<64, true><<<dim3(grid), dim3(kDecThreads), smem, s>>>(enc, W0, b0, W1, b1, W2, b2, rgb, P, out_dim);
-      else decoder_fwd_split_kernel<64, false><<<dim3(grid), dim3(kDecThreads), smem, s>>>(enc, W0, b0, W1, b1, W2, b2, rgb, P, out_dim);
-    }
-    GNGF_RETURN_LAUNCH();
-  }
-#endif
   DISPATCH_KIN(in_dim, {
     using Kern = void (*)(const float*, const float*, const float*, const float*, const float*, const float*, const float*, float*,
                           float*, int64_t, int, int);
@@ -1435,16 +1397,6 @@ extern "C" int gngf_decoder_bwd(const float* enc, const float* rgb, const float*
       hipError_t e = zero_async(zero_fill, sizeof(float) * (size_t)zero_floats, s);
       if (e != hipSuccess) return (int)e;
     }
-#if defined(GNGF_DECODER_SPLIT_KERNELS)
-    if (decoder_split_applies(in_dim) && in_dim == 32) {
-      const size_t main_loop = SplitBwd<32>::kMainBytes, epilogue = sizeof(float) * 4 * (size_t)nslab;
-      const size_t smem = main_loop > epilogue ? main_loop : epilogue;
-      auto fn = leaky ? decoder_bwd_split_kernel<32, true> : decoder_bwd_split_kernel<32, false>;
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) return (int)e;
-      fn<<<dim3((unsigned)nslabs), dim3(kDecThreads), smem, s>>>(enc, rgb, drgb, W0, b0, W1, b1, W2, denc, slabs, P, out_dim, target, gloss);
-    } else
-#endif
     if (g_decoder_bwd_hybrid && in_dim == 32 && hidden) {
       const size_t smem = bwd_smem_bytes_hybrid(out_dim);
       auto fn = leaky ? decoder_bwd_kernel<32, true, true, false, true> : decoder_bwd_kernel<32, false, true, false, true>;

@@ -1,11 +1,10 @@
-// Split-bf16 decoder kernels (included by decoder.hip inside namespace gngf).
+// Split-bf16 helpers of the decoder's hybrid backward and training kernels (included by decoder.hip inside namespace gngf).
 //
-// The same fused MLP as decoder_fwd_kernel / decoder_bwd_kernel, with every 64-wide (and the input) product moved from
-// v_mfma_f32_32x32x2_f32 to v_mfma_f32_32x32x16_bf16: each fp32 operand value is split EXACTLY into three bf16 terms by
-// truncation, x = hi + mid + lo (8 + 8 + 8 significant bits: `hi` is the upper half of the fp32 word, the residuals are
+// A product moves from v_mfma_f32_32x32x2_f32 to v_mfma_f32_32x32x16_bf16: each fp32 operand value is split EXACTLY into three
+// bf16 terms by truncation, x = hi + mid + lo (8 + 8 + 8 significant bits: `hi` is the upper half of the fp32 word, the residuals are
 // exact fp32 subtractions), and a product is the sum of six of the nine cross terms accumulated in fp32,
 //     a b ~= hi lo + lo hi + mid mid + hi mid + mid hi + hi hi          (dropped: mid lo, lo mid, lo lo  <  2^-23 |a b|)
-// i.e. at the accuracy of an fp32 fma chain (tests/test_gpu_dense.py compares both decoders with a float64 evaluation).
+// i.e. at the accuracy of an fp32 fma chain (tests/test_gpu_dense.py compares the decoders with a float64 evaluation).
 // Why: six bf16 MFMAs take 6 x 32 cycles for a 32x32x16 block that costs 8 x 64 cycles on the fp32 pipe, and — measured,
 // tools/micro/gen_mfma_bf16_mix.py — VALU instructions issue underneath a bf16 MFMA (4 per MFMA for free), which they never
 // do under an fp32 one: the splitting (5.5 VALU instructions per value) mostly disappears under the matrix pipe.
@@ -14,12 +13,8 @@
 // registers 8c .. 8c+7 of both lane halves ARE k-chunk c of the next layer's B operand — no LDS round trip between layers.
 //   k-chunk (t, c) of a 64-wide activation, lane half h, element j  <->  feature 32 t + crow(8 c + j, h)
 //   k-chunk c of the input row,            lane half h, element j  <->  input feature h KIN/2 + 8 c + j
-// With the matrix work 2.7x cheaper the saved hidden layers (512 B/pixel each way) would make both kernels HBM-bound, so
-// the backward kernel recomputes them (72 bf16 MFMAs per 32 pixels) and the forward kernel writes nothing but rgb.
+// (An all-bf16 decoder pair built on the same split was measured and dropped: DESIGN.md §3.)
 
-#ifndef GNGF_SPLIT_EXP
-#define GNGF_SPLIT_EXP 0
-#endif
 struct Planes { u32x4 hi, mid, lo; };
 
 __device__ __forceinline__ unsigned pack_hi16(float b, float a) {      // (upper half of b) : (upper half of a)
@@ -31,15 +26,6 @@ __device__ __forceinline__ float trunc_residual(float v) { return v - __uint_as_
 __device__ __forceinline__ Planes split8(float x0, float x1, float x2, float x3, float x4, float x5, float x6, float x7) {
   const float x[8] = {x0, x1, x2, x3, x4, x5, x6, x7};
   unsigned hi[4], mid[4], lo[4];
-#if GNGF_SPLIT_EXP == 1        // timing experiment: no VALU work in the split
-  {
-    Planes p;
-    p.hi = u32x4{__float_as_uint(x0), __float_as_uint(x1), __float_as_uint(x2), __float_as_uint(x3)};
-    p.mid = u32x4{__float_as_uint(x4), __float_as_uint(x5), __float_as_uint(x6), __float_as_uint(x7)};
-    p.lo = p.hi;
-    return p;
-  }
-#endif
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const float a = x[2 * q], b = x[2 * q + 1];
@@ -55,23 +41,10 @@ __device__ __forceinline__ Planes split8(float x0, float x1, float x2, float x3,
 
 using bf16x8_t = __attribute__((ext_vector_type(8))) __bf16;
 __device__ __forceinline__ f32x16 mfma_b(u32x4 a, u32x4 b, f32x16 c) {
-#if GNGF_SPLIT_EXP == 2        // timing experiment: no matrix instructions
-  c[0] += __uint_as_float(a.x ^ b.x); c[5] += __uint_as_float(a.y ^ b.y); c[10] += __uint_as_float(a.z ^ b.z); c[15] += __uint_as_float(a.w ^ b.w);
-  return c;
-#endif
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 }
-// acc += A B over one k-chunk, six cross terms, smallest first
-__device__ __forceinline__ f32x16 mfma_split(const Planes& a, const Planes& b, f32x16 acc) {
-  acc = mfma_b(a.hi, b.lo, acc);
-  acc = mfma_b(a.lo, b.hi, acc);
-  acc = mfma_b(a.mid, b.mid, acc);
-  acc = mfma_b(a.hi, b.mid, acc);
-  acc = mfma_b(a.mid, b.hi, acc);
-  acc = mfma_b(a.hi, b.hi, acc);
-  return acc;
-}
-// the same for two output tiles sharing the B operand, interleaved (independent accumulators back to back)
+// acc += A B over one k-chunk, six cross terms, smallest first, for two output tiles sharing the B operand, interleaved
+// (independent accumulators back to back)
 __device__ __forceinline__ void mfma_split2(const Planes& a0, const Planes& a1, const Planes& b, f32x16& c0, f32x16& c1) {
   c0 = mfma_b(a0.hi, b.lo, c0);  c1 = mfma_b(a1.hi, b.lo, c1);
   c0 = mfma_b(a0.lo, b.hi, c0);  c1 = mfma_b(a1.lo, b.hi, c1);
@@ -81,562 +54,9 @@ __device__ __forceinline__ void mfma_split2(const Planes& a0, const Planes& a1, 
   c0 = mfma_b(a0.hi, b.hi, c0);  c1 = mfma_b(a1.hi, b.hi, c1);
 }
 
-// Activation as ONE compiler-visible VALU instruction (v_med3_f32): the inline-asm v_max of the fp32 kernels is invisible to
-// the hazard recogniser, and here the next MFMA may read the register two instructions later (VALU write -> MFMA read needs
-// wait states the compiler only inserts for instructions it knows).
-template <bool LEAKY> __device__ __forceinline__ float act_split(float z) {
-  return __builtin_amdgcn_fmed3f(z, LEAKY ? 0.01f * z : 0.f, __builtin_inff());
-}
-
 // k index of a 64-wide activation at chunk cc (= 2 t + c), lane half h, element j
 __device__ __forceinline__ int kmapS(int cc, int h, int j) { return 32 * (cc >> 1) + crow(8 * (cc & 1) + j, h); }
 
-// ------------------------------------------------------------------------------------------------ forward
-// A fragments (weights) as bf16 planes in LDS, one 16-byte read per lane and fragment:  frag[(f * 3 + plane) * 64 + lane],
-//   f = 2 c + t            (layer 1, k-chunk c of the input, output tile t)         f in [0, 2 C0)
-//   f = 2 C0 + 2 cc + t    (layer 2, k-chunk cc of the hidden layer)                 8 fragments
-// Two waves per SIMD (256 registers each): while one wave splits an accumulator tile on the VALU the other one's MFMAs run
-// — the dependent phases (matrix run -> activation + split -> matrix run) need no hand-made software pipeline.
-#if defined(GNGF_DECODER_SPLIT_KERNELS)      // the all-bf16 kernel pair is a measured negative result: built only on request (make SPLIT=1)
-template <int KIN> struct SplitFwd {
-  static constexpr int C0 = KIN / 16;
-  static constexpr int kFrags = 2 * C0 + 8;
-  static constexpr int kFragWords = kFrags * 3 * 64 * 4;        // 32-bit words
-  static constexpr int kBiasWords = 4 * 64 * 16;                // bias tiles in accumulator layout: [(layer, t)][lane][16]
-};
-#endif
+// A fragments (weights) as bf16 planes in LDS, one 16-byte read per lane and fragment:  frag[(f * 3 + plane) * 64 + lane]
 __device__ __forceinline__ void store_planes(u32x4* dst, const Planes& p) { dst[0] = p.hi; dst[64] = p.mid; dst[128] = p.lo; }
 __device__ __forceinline__ Planes load_planes(const u32x4* src) { Planes p; p.hi = src[0]; p.mid = src[64]; p.lo = src[128]; return p; }
-
-#if defined(GNGF_DECODER_SPLIT_KERNELS)
-template <int KIN, bool LEAKY>
-__global__ void __launch_bounds__(kDecThreads, 2)
-decoder_fwd_split_kernel(const float* __restrict__ X, const float* __restrict__ W0, const float* __restrict__ b0,
-                         const float* __restrict__ W1, const float* __restrict__ b1, const float* __restrict__ W2,
-                         const float* __restrict__ b2, float* __restrict__ Y, int64_t P, int out_dim) {
-  constexpr int S0 = KIN / 2;            // input features per lane half
-  constexpr int C0 = KIN / 16;           // k-chunks of layer 1
-  constexpr int in_dim = KIN;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
-  const int64_t ntiles = (P + 127) / 128;
-  extern __shared__ float smem_f[];
-  u32x4* frag = reinterpret_cast<u32x4*>(smem_f);                          // kFragWords
-  f32x16* biasL = reinterpret_cast<f32x16*>(smem_f + SplitFwd<KIN>::kFragWords);
-  float* raw = smem_f + SplitFwd<KIN>::kFragWords + SplitFwd<KIN>::kBiasWords;
-  stage_raw(raw, W0, b0, W1, b1, W2, b2, in_dim, out_dim);
-  const RawOff o = raw_offsets(in_dim);
-  // every wave splits a quarter of the fragments
-  for (int f = wave; f < SplitFwd<KIN>::kFrags; f += 4) {
-    float v[8];
-    if (f < 2 * C0) {
-      const int c = f >> 1, t = f & 1;
-      const float* r0 = raw + o.w0 + (32 * t + i) * (in_dim + 1) + h * S0 + 8 * c;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = r0[j];
-    } else {
-      const int cc = (f - 2 * C0) >> 1, t = f & 1;
-      const float* r1 = raw + o.w1 + (32 * t + i) * 65;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = r1[kmapS(cc, h, j)];
-    }
-    store_planes(frag + f * 3 * 64 + lane, split8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]));
-  }
-  float w2a[32];
-  if (wave < 2) {                                                     // (identical for every wave: written once)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      f32x16 bv;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) bv[r] = raw[(wave == 0 ? o.b0 : o.b1) + 32 * t + crow(r, h)];
-      biasL[(2 * wave + t) * 64 + lane] = bv;
-    }
-  }
-  const int ch = lane & 3;
-#pragma unroll
-  for (int s2 = 0; s2 < 32; ++s2) w2a[s2] = raw[o.w2 + ch * 65 + kmapC(s2, h)];
-  float b2v[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) b2v[c] = raw[o.b2 + c];
-  __syncthreads();
-
-  const unsigned xoff = (unsigned)(((wave * 32 + i) * in_dim + h * S0) * 4);
-  const unsigned yoff = (unsigned)(((wave * 32 + i) * out_dim) * 4);
-  auto fetch = [&](int64_t t, float* dst) {
-    const int64_t tt = t < ntiles ? t : ntiles;          // past the end: an empty window, every lane reads zeros
-    int64_t rem = (P - tt * 128) * in_dim * 4;
-    rem = rem < 0 ? 0 : (rem > 128 * in_dim * 4 ? 128 * in_dim * 4 : rem);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X) + tt * 128 * in_dim, 0, (int)rem, 0x00020000);
-#pragma unroll
-    for (int k = 0; k < S0 / 4; ++k) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, xoff + 16 * k, 0, 0);
-      dst[4 * k] = __uint_as_float(v.x); dst[4 * k + 1] = __uint_as_float(v.y);
-      dst[4 * k + 2] = __uint_as_float(v.z); dst[4 * k + 3] = __uint_as_float(v.w);
-    }
-  };
-  float xr[S0], xn[S0];
-  fetch(blockIdx.x, xr);
-#if defined(GNGF_STAMPS)
-  unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast) :: "memory");
-#endif
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    STAMP(0);
-    fetch(tile + gridDim.x, xn);                          // lands under this tile's matrix work
-    int lo = lane;
-    asm volatile("" : "+v"(lo));                          // opaque per tile: the fragment reads stay in the loop (144 registers otherwise)
-    const u32x4* fl = frag + lo;
-    f32x16 acc1[2] = {biasL[lo], biasL[64 + lo]}, acc2[2];
-#pragma unroll
-    for (int c = 0; c < C0; ++c) {
-      const Planes a0 = load_planes(fl + (2 * c) * 3 * 64), a1 = load_planes(fl + (2 * c + 1) * 3 * 64);
-      const Planes xs = split8(xr[8 * c], xr[8 * c + 1], xr[8 * c + 2], xr[8 * c + 3], xr[8 * c + 4], xr[8 * c + 5], xr[8 * c + 6], xr[8 * c + 7]);
-      mfma_split2(a0, a1, xs, acc1[0], acc1[1]);
-    }
-    STAMP(1);
-    acc2[0] = biasL[128 + lo]; acc2[1] = biasL[192 + lo];
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc) {
-      const int t = cc >> 1, r0 = 8 * (cc & 1);
-      const Planes a0 = load_planes(fl + (2 * C0 + 2 * cc) * 3 * 64), a1 = load_planes(fl + (2 * C0 + 2 * cc + 1) * 3 * 64);
-      float a[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a[j] = act_split<LEAKY>(acc1[t][r0 + j]);
-      const Planes hs = split8(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]);
-      mfma_split2(a0, a1, hs, acc2[0], acc2[1]);
-    }
-    STAMP(2);
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc2[t][r] = act_split<LEAKY>(acc2[t][r]);
-    f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s2 = 0; s2 < 32; s2 += 2) {
-      d0 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2a[s2], acc2[s2 >> 4][s2 & 15], d0, 0, 0, 0);
-      d1 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2a[s2 + 1], acc2[(s2 + 1) >> 4][(s2 + 1) & 15], d1, 0, 0, 0);
-    }
-    STAMP(3);
-    {
-      int64_t rem = (P - tile * 128) * out_dim * 4;
-      rem = rem > 128 * out_dim * 4 ? 128 * out_dim * 4 : rem;
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(Y + tile * 128 * out_dim, 0, (int)rem, 0x00020000);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float dc = d0[c] + d1[c];
-        const float z = dc + __shfl_xor(dc, 32, 64) + b2v[c];
-        const float y = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z * -1.4426950408889634f));
-        const unsigned off = (h == 0 && c < out_dim) ? yoff + 4u * c : 0x40000000u;
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y), rs, off, 0, 0);
-      }
-    }
-    STAMP(4);
-#pragma unroll
-    for (int s = 0; s < S0; ++s) xr[s] = xn[s];
-    STAMP(5);
-  }
-#if defined(GNGF_STAMPS)
-  if (blockIdx.x == 7 && threadIdx.x == 0)
-    for (int k = 0; k < 10; ++k) g_fstamps[k] = ph[k];
-#endif
-}
-
-// ------------------------------------------------------------------------------------------------ backward
-// One wave per SIMD (the weight-gradient tiles alone are 96 accumulator registers).  The hidden layers are recomputed.
-// Products on the bf16 pipe (6 cross terms each): recompute L1 / L2, dh1 = W1^T dz2, d enc = W0^T dz1 with the pixel on the
-// lane (operands straight from the accumulator registers, as in the forward kernel), and the weight gradients
-// dW1 = dz2^T h1, dW0 = dz1^T x, which contract over the PIXEL index: their operands are transposed through per-wave LDS
-// images that already hold the three bf16 planes — a lane writes the upper halves of v, v - hi, v - hi - mid (the values
-// of the exact residual chain the register operand needs anyway) as 16-bit stores, and the fragment of the transposed
-// product is ONE 16-byte read per plane, no VALU work on the reading side.
-//   image plane = [64 rows][32 pixels] bf16 = 4 KB, 3 planes; rows and 16-byte chunks swizzled so that both the 16-bit
-//   stores (pixel on the lane, rows 4 apart in the two lane halves) and the 16-byte reads (row on the lane) are conflict-free:
-//     hidden feature f = 32 t + crow(r, h):  row byte offset 2048 t + 512 (r >> 2) + 128 (r & 3) + 64 h,  chunk (p >> 3) ^ (r & 3)
-//     input feature  x = 16 h + s:            row byte offset 256 (s >> 1) + 128 h + 64 (s & 1),            chunk (p >> 3) ^ ((s >> 1) & 3)
-// Bias gradients ride on the same pipe: dz^T times a B operand that is 1 in ONE column (column 0: db1, column 1: db0) — three
-// MFMAs per fragment (hi, mid, lo times 1.0) into one shared accumulator tile pair.  The 3-4 wide last layer stays on the fp32
-// matrix instructions exactly as in decoder_bwd_kernel (dh2 = W2^T dz3 on 32x32x2, dW2 on 4x4x1 through an fp32 image).
-template <int KIN> struct SplitBwd {
-  static constexpr int kFragBytes = 16 * 3 * 1024;                       // W1 (8) and W1^T (8) fragments
-  static constexpr int kBiasBytes = 2 * kH * 4;
-  static constexpr int kImgBytes = 3 * 4096;
-  static constexpr int kWaveBytes = 2 * kImgBytes + 4 * kImgStride * 4;  // imgA | imgB | imgZ (dz3 rows, fp32)
-  static constexpr int kMainBytes = kFragBytes + kBiasBytes + 4 * kWaveBytes;
-};
-
-// The images are written as 16-bit words / floats and read back as 16-byte vectors / float pairs: every access goes through
-// a may_alias type (type-based alias analysis would otherwise let the reads move above the stores).
-typedef unsigned short __attribute__((may_alias)) u16_any;
-typedef u32x4 __attribute__((may_alias)) u32x4_any;
-typedef float __attribute__((may_alias)) f32_any;
-typedef f32x2 __attribute__((may_alias)) f32x2_any;
-__device__ __forceinline__ void store_hi16(char* p, float v) {           // upper half of the fp32 word (ds_write_b16_d16_hi)
-  *reinterpret_cast<u16_any*>(p) = (unsigned short)(__float_as_uint(v) >> 16);
-}
-// the three planes of eight values: packed for the register operand, and stored to an image (one 16-bit store per plane)
-struct Chain { float v, r1, r2; };
-__device__ __forceinline__ Chain chain3(float v) { Chain c; c.v = v; c.r1 = trunc_residual(v); c.r2 = trunc_residual(c.r1); return c; }
-__device__ __forceinline__ Planes pack_chains(const Chain (&c)[8]) {
-  Planes p;
-  p.hi = u32x4{pack_hi16(c[1].v, c[0].v), pack_hi16(c[3].v, c[2].v), pack_hi16(c[5].v, c[4].v), pack_hi16(c[7].v, c[6].v)};
-  p.mid = u32x4{pack_hi16(c[1].r1, c[0].r1), pack_hi16(c[3].r1, c[2].r1), pack_hi16(c[5].r1, c[4].r1), pack_hi16(c[7].r1, c[6].r1)};
-  p.lo = u32x4{pack_hi16(c[1].r2, c[0].r2), pack_hi16(c[3].r2, c[2].r2), pack_hi16(c[5].r2, c[4].r2), pack_hi16(c[7].r2, c[6].r2)};
-  return p;
-}
-__device__ __forceinline__ void store_chain(char* p, const Chain& c) { store_hi16(p, c.v); store_hi16(p + 4096, c.r1); store_hi16(p + 8192, c.r2); }
-__device__ __forceinline__ Planes load_img(const char* p) {
-  Planes r;
-  r.hi = *reinterpret_cast<const u32x4_any*>(p); r.mid = *reinterpret_cast<const u32x4_any*>(p + 4096); r.lo = *reinterpret_cast<const u32x4_any*>(p + 8192);
-  return r;
-}
-// acc += A * ones (the B operand is exactly representable: three terms)
-__device__ __forceinline__ f32x16 mfma_ones(const Planes& a, u32x4 ones, f32x16 acc) {
-  acc = mfma_b(a.lo, ones, acc);
-  acc = mfma_b(a.mid, ones, acc);
-  acc = mfma_b(a.hi, ones, acc);
-  return acc;
-}
-
-template <int KIN, bool LEAKY>
-__global__ void __launch_bounds__(kDecThreads, 1)
-decoder_bwd_split_kernel(const float* __restrict__ X, const float* __restrict__ Yout, const float* __restrict__ dY,
-                         const float* __restrict__ W0, const float* __restrict__ b0, const float* __restrict__ W1,
-                         const float* __restrict__ b1, const float* __restrict__ W2, float* __restrict__ dX,
-                         float* __restrict__ slabs, int64_t P, int out_dim, const float* __restrict__ target,
-                         const float* __restrict__ gloss) {
-  static_assert(KIN == 32, "64-wide input: not written yet");
-  constexpr int in_dim = KIN, S0 = KIN / 2;
-  using SB = SplitBwd<KIN>;
-  if (blockIdx.x == 0 && threadIdx.x == 0) { g_bwd_span[1] = 0ull; g_bwd_span[0] = wall_clock64(); }
-  extern __shared__ float smem[];
-  char* lds = reinterpret_cast<char*>(smem);
-  u32x4* frag = reinterpret_cast<u32x4*>(lds);                              // [16 fragments][3 planes][64 lanes]
-  float* biasL = reinterpret_cast<float*>(lds + SB::kFragBytes);           // b0 | b1
-  char* waves = lds + SB::kFragBytes + SB::kBiasBytes;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
-  const int nslab = slab_size(in_dim, out_dim);
-
-  float* raw = reinterpret_cast<float*>(waves);                             // the image area is free until the main loop starts
-  stage_raw(raw, W0, b0, W1, b1, W2, nullptr, in_dim, out_dim);
-  const RawOff ro = raw_offsets(in_dim);
-  for (int f = wave; f < 16; f += 4) {                                      // LDS fragments: W1 (layer-2 recompute), W1^T (dh1)
-    const int cc = (f & 7) >> 1, t = f & 1;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      v[j] = f < 8 ? raw[ro.w1 + (32 * t + i) * 65 + kmapS(cc, h, j)] : raw[ro.w1 + kmapS(cc, h, j) * 65 + 32 * t + i];
-    store_planes(frag + f * 3 * 64 + lane, split8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]));
-  }
-  for (int e = threadIdx.x; e < 2 * kH; e += kDecThreads) biasL[e] = e < kH ? raw[ro.b0 + e] : raw[ro.b1 + e - kH];
-  Planes fl1[2][2], fdx[4];                                                 // register fragments: W0 (layer 1), W0^T (d enc)
-#pragma unroll
-  for (int c = 0; c < 2; ++c)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const float* r0 = raw + ro.w0 + (32 * t + i) * (in_dim + 1) + h * S0 + 8 * c;
-      fl1[c][t] = split8(r0[0], r0[1], r0[2], r0[3], r0[4], r0[5], r0[6], r0[7]);
-    }
-#pragma unroll
-  for (int cc = 0; cc < 4; ++cc) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = raw[ro.w0 + kmapS(cc, h, j) * (in_dim + 1) + i];
-    fdx[cc] = split8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
-  }
-  float fa2[2][2];                                                          // W2^T fragments of dh2 (fp32 32x32x2: k = lane half)
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int sk = 0; sk < 2; ++sk) fa2[t][sk] = raw[ro.w2 + (2 * sk + h) * 65 + 32 * t + i];
-  __syncthreads();
-
-  char* imgA = waves + wave * SB::kWaveBytes;
-  char* imgB = imgA + SB::kImgBytes;
-  f32_any* imgZ = reinterpret_cast<f32_any*>(imgB + SB::kImgBytes);
-  f32_any* imgH = reinterpret_cast<f32_any*>(imgA);                             // fp32 [64][34] image of h2 for dW2 (before dz2 lands in imgA)
-  const u32x4 ones1 = i == 0 ? u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u} : u32x4{0u, 0u, 0u, 0u};
-  const u32x4 ones0 = i == 1 ? u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u} : u32x4{0u, 0u, 0u, 0u};
-
-  f32x16 dW1acc[2][2], dW0acc[2], dbacc[2];
-  f32x4 dW2acc = {0.f, 0.f, 0.f, 0.f};
-  float db2acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int a = 0; a < 2; ++a) { dW1acc[a][0] = 0; dW1acc[a][1] = 0; dW0acc[a] = 0; dbacc[a] = 0; }
-
-  const int64_t ntiles = (P + 127) / 128;
-  const unsigned xoff = (unsigned)(((wave * 32 + i) * in_dim + h * S0) * 4);
-  const unsigned yoff = (unsigned)(((wave * 32 + i) * out_dim) * 4);
-  const bool fused_loss = target != nullptr;
-  const float* dsrc = fused_loss ? target : dY;
-  const float kloss = fused_loss ? gloss[0] * (2.0f / (float)(P * out_dim)) : 0.f;
-  auto tile_window = [&](int64_t t, int64_t& tt, int& rows) {
-    tt = t < ntiles ? t : ntiles;
-    int64_t rem = P - tt * 128;
-    rows = (int)(rem < 0 ? 0 : (rem > 128 ? 128 : rem));
-  };
-  auto fetch_x = [&](int64_t t, float* dst) {
-    int64_t tt; int rows;
-    tile_window(t, tt, rows);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X) + tt * 128 * in_dim, 0, rows * in_dim * 4, 0x00020000);
-#pragma unroll
-    for (int k = 0; k < S0 / 4; ++k) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rx, xoff + 16 * k, 0, 0);
-      dst[4 * k] = __uint_as_float(v.x); dst[4 * k + 1] = __uint_as_float(v.y);
-      dst[4 * k + 2] = __uint_as_float(v.z); dst[4 * k + 3] = __uint_as_float(v.w);
-    }
-  };
-  auto fetch_y = [&](int64_t t, float* yn, float* dyn) {
-    int64_t tt; int rows;
-    tile_window(t, tt, rows);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Yout) + tt * 128 * out_dim, 0, rows * out_dim * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dsrc) + tt * 128 * out_dim, 0, rows * out_dim * 4, 0x00020000);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const unsigned off = c < out_dim ? yoff + 4u * c : 0x40000000u;
-      yn[c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, off, 0, 0));
-      dyn[c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, off, 0, 0));
-    }
-  };
-  float xr[S0], xn[S0], yr[4], dyr[4], yn[4], dyn[4];
-  fetch_x(blockIdx.x, xr);
-  fetch_y(blockIdx.x, yr, dyr);
-  unsigned dxmax = 0u;
-#if defined(GNGF_STAMPS)
-  unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast) :: "memory");
-#endif
-
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    fetch_x(tile + gridDim.x, xn);
-    fetch_y(tile + gridDim.x, yn, dyn);
-    int lo = lane;
-    asm volatile("" : "+v"(lo));                           // opaque per tile: LDS fragment reads stay inside the loop
-    const int li = lo & 31, lh = lo >> 5;
-    const u32x4* fl = frag + lo;
-    // per-lane parts of the image addresses (see the layout note above)
-    char* wA[4]; char* wB[4]; char* wX[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int lp = 16 * ((li >> 3) ^ s) + 2 * (li & 7);
-      wA[s] = imgA + 64 * lh + lp; wB[s] = imgB + 64 * lh + lp; wX[s] = imgB + 128 * lh + lp;
-    }
-    const int rrow = 512 * (li >> 3) + 128 * (li & 3) + 64 * ((li >> 2) & 1);
-    const int xrow = 256 * ((li & 15) >> 1) + 128 * (li >> 4) + 64 * (li & 1);
-    const char* rA[2]; const char* rB[2]; const char* rX[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      rA[c] = imgA + rrow + 16 * ((2 * c + lh) ^ (li & 3));
-      rB[c] = imgB + rrow + 16 * ((2 * c + lh) ^ (li & 3));
-      rX[c] = imgB + xrow + 16 * ((2 * c + lh) ^ ((li >> 1) & 3));
-    }
-
-    STAMP(0);
-    // ---- layer 1 (recompute): h1^T = W0 x^T + b0
-    f32x16 acc1[2], acc2[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 q0 = *reinterpret_cast<const f32x4*>(biasL + 32 * t + 8 * g + 4 * lh);
-        const f32x4 q1 = *reinterpret_cast<const f32x4*>(biasL + kH + 32 * t + 8 * g + 4 * lh);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { acc1[t][4 * g + e] = q0[e]; acc2[t][4 * g + e] = q1[e]; }
-      }
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const Planes xs = split8(xr[8 * c], xr[8 * c + 1], xr[8 * c + 2], xr[8 * c + 3], xr[8 * c + 4], xr[8 * c + 5], xr[8 * c + 6], xr[8 * c + 7]);
-      mfma_split2(fl1[c][0], fl1[c][1], xs, acc1[0], acc1[1]);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc1[t][r] = act_split<LEAKY>(acc1[t][r]);          // h1
-    STAMP(1);
-    // ---- layer 2 (recompute): h2^T = W1 h1^T + b1; the h1 planes go to image B on the way
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc) {
-      const int t = cc >> 1, r0 = 8 * (cc & 1);
-      Chain ch[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        ch[j] = chain3(acc1[t][r0 + j]);
-        const int r = r0 + j;
-        store_chain(wB[r & 3] + 2048 * t + 512 * (r >> 2) + 128 * (r & 3), ch[j]);
-      }
-      const Planes hs = pack_chains(ch);
-      mfma_split2(load_planes(fl + (2 * cc) * 3 * 64), load_planes(fl + (2 * cc + 1) * 3 * 64), hs, acc2[0], acc2[1]);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc2[t][r] = act_split<LEAKY>(acc2[t][r]);          // h2
-    STAMP(2);
-    // ---- dz3, dh2^T = W2^T dz3^T (fp32 pipe, k = output channel), dW2 on 4x4x1 through the fp32 image of h2
-    float dz3[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float dy = fused_loss ? kloss * (yr[c] - dyr[c]) : dyr[c];
-      dz3[c] = dy * (yr[c] * (1.f - yr[c]));
-      db2acc[c] += dz3[c];
-      imgZ[c * kImgStride + li] = dz3[c];
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) imgH[(32 * t + (r & 3) + 8 * (r >> 2) + 4 * lh) * kImgStride + li] = acc2[t][r];
-    f32x16 d2[2];
-    {
-      const float bs0 = lh == 0 ? dz3[0] : dz3[1], bs1 = lh == 0 ? dz3[2] : dz3[3];
-      f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      d2[0] = MFMA(fa2[0][0], bs0, z); d2[1] = MFMA(fa2[1][0], bs0, z);
-      d2[0] = MFMA(fa2[0][1], bs1, d2[0]); d2[1] = MFMA(fa2[1][1], bs1, d2[1]);
-    }
-    {
-      const f32_any* zrow = imgZ + (lo & 3) * kImgStride;
-      const f32_any* hrow = imgH + lo * kImgStride;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const f32x2 av = *reinterpret_cast<const f32x2_any*>(zrow + 2 * q), bv = *reinterpret_cast<const f32x2_any*>(hrow + 2 * q);
-        dW2acc = __builtin_amdgcn_mfma_f32_4x4x1f32(av.x, bv.x, dW2acc, 0, 0, 0);
-        dW2acc = __builtin_amdgcn_mfma_f32_4x4x1f32(av.y, bv.y, dW2acc, 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) d2[t][r] = hidden_dsel<LEAKY>(acc2[t][r], d2[t][r]);   // dz2
-    STAMP(3);
-    // ---- dh1^T = W1^T dz2^T; the dz2 planes go to image A (over the h2 image, whose reads were issued above)
-    f32x16 d1[2];
-    d1[0] = 0; d1[1] = 0;
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc) {
-      const int t = cc >> 1, r0 = 8 * (cc & 1);
-      Chain ch[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        ch[j] = chain3(d2[t][r0 + j]);
-        const int r = r0 + j;
-        store_chain(wA[r & 3] + 2048 * t + 512 * (r >> 2) + 128 * (r & 3), ch[j]);
-      }
-      const Planes zs = pack_chains(ch);
-      mfma_split2(load_planes(fl + (8 + 2 * cc) * 3 * 64), load_planes(fl + (8 + 2 * cc + 1) * 3 * 64), zs, d1[0], d1[1]);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) d1[t][r] = hidden_dsel<LEAKY>(acc1[t][r], d1[t][r]);   // dz1
-    STAMP(4);
-    // ---- dW1 += dz2^T h1, db1 += dz2^T 1
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const Planes a0 = load_img(rA[c]), a1 = load_img(rA[c] + 2048), b0p = load_img(rB[c]), b1p = load_img(rB[c] + 2048);
-      dW1acc[0][0] = mfma_split(a0, b0p, dW1acc[0][0]);
-      dW1acc[0][1] = mfma_split(a0, b1p, dW1acc[0][1]);
-      dW1acc[1][0] = mfma_split(a1, b0p, dW1acc[1][0]);
-      dW1acc[1][1] = mfma_split(a1, b1p, dW1acc[1][1]);
-      dbacc[0] = mfma_ones(a0, ones1, dbacc[0]);
-      dbacc[1] = mfma_ones(a1, ones1, dbacc[1]);
-    }
-    STAMP(5);
-    // ---- d enc^T = W0^T dz1^T; the dz1 planes go to image A (over dz2), the x planes to image B (over h1)
-    f32x16 dxv;
-    dxv = 0;
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc) {
-      const int t = cc >> 1, r0 = 8 * (cc & 1);
-      Chain ch[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        ch[j] = chain3(d1[t][r0 + j]);
-        const int r = r0 + j;
-        store_chain(wA[r & 3] + 2048 * t + 512 * (r >> 2) + 128 * (r & 3), ch[j]);
-      }
-      dxv = mfma_split(fdx[cc], pack_chains(ch), dxv);
-    }
-#pragma unroll
-    for (int s = 0; s < S0; ++s) store_chain(wX[(s >> 1) & 3] + 256 * (s >> 1) + 64 * (s & 1), chain3(xr[s]));
-    STAMP(6);
-    // ---- dW0 += dz1^T x, db0 += dz1^T 1
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const Planes a0 = load_img(rA[c]), a1 = load_img(rA[c] + 2048), bx = load_img(rX[c]);
-      dW0acc[0] = mfma_split(a0, bx, dW0acc[0]);
-      dW0acc[1] = mfma_split(a1, bx, dW0acc[1]);
-      dbacc[0] = mfma_ones(a0, ones0, dbacc[0]);
-      dbacc[1] = mfma_ones(a1, ones0, dbacc[1]);
-    }
-    STAMP(7);
-    // ---- d enc out
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const unsigned a = __float_as_uint(dxv[r]) & 0x7fffffffu;
-      dxmax = a > dxmax ? a : dxmax;
-    }
-    {
-      int64_t rem = P - tile * 128;
-      rem = rem > 128 ? 128 : rem;
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dX + tile * 128 * in_dim, 0, (int)rem * in_dim * 4, 0x00020000);
-      const unsigned base = (unsigned)((wave * 32 + i) * in_dim) * 4u;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const u32x4 v = {__float_as_uint(dxv[4 * g]), __float_as_uint(dxv[4 * g + 1]), __float_as_uint(dxv[4 * g + 2]), __float_as_uint(dxv[4 * g + 3])};
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs, base + 4u * (8 * g + 4 * h), 0, 0);
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < S0; ++s) xr[s] = xn[s];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { yr[c] = yn[c]; dyr[c] = dyn[c]; }
-    STAMP(8);
-  }
-#if defined(GNGF_STAMPS)
-  if (blockIdx.x == 7 && threadIdx.x == 0)
-    for (int k = 0; k < 10; ++k) g_stamps[k] = ph[k];
-#endif
-
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const unsigned ov = (unsigned)__shfl_xor((int)dxmax, o, 64); dxmax = ov > dxmax ? ov : dxmax; }
-  // ---- wave accumulators -> workgroup slab (same slab layout and reduction as decoder_bwd_kernel)
-  __syncthreads();
-  float* region = smem + wave * nslab;
-  float* sW0 = region;
-  float* sW1 = sW0 + kH * in_dim;
-  float* sW2 = sW1 + kH * kH;
-  float* sb0 = sW2 + out_dim * kH;
-  float* sb1 = sb0 + kH;
-  float* sb2 = sb1 + kH;
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = 32 * ti + crow(r, h);
-#pragma unroll
-      for (int tj = 0; tj < 2; ++tj) sW1[row * kH + 32 * tj + i] = dW1acc[ti][tj][r];
-      sW0[row * in_dim + i] = dW0acc[ti][r];
-      if (i == 0) sb1[row] = dbacc[ti][r];
-      if (i == 1) sb0[row] = dbacc[ti][r];
-    }
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-    if (c < out_dim) sW2[c * kH + lane] = dW2acc[c];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    float v = h == 0 ? db2acc[c] : 0.f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0 && c < out_dim) sb2[c] = v;
-  }
-  if (lane == 0) region[nslab - 1] = __uint_as_float(dxmax);
-  __syncthreads();
-  float* out = slabs + (int64_t)blockIdx.x * nslab;
-  for (int e = threadIdx.x; e < nslab - 1; e += kDecThreads)
-    out[e] = (smem[e] + smem[nslab + e]) + (smem[2 * nslab + e] + smem[3 * nslab + e]);
-  if (threadIdx.x == 0) {
-    unsigned mx = 0u;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const unsigned v = __float_as_uint(smem[w * nslab + nslab - 1]); mx = v > mx ? v : mx; }
-    out[nslab - 1] = __uint_as_float(mx);
-    atomicMax(&g_bwd_span[1], (unsigned long long)wall_clock64());
-  }
-}
-#endif  // GNGF_DECODER_SPLIT_KERNELS

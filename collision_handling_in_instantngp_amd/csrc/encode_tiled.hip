@@ -1319,9 +1319,10 @@ typedef BinJobDev BinScatterRide;   // (bin_scatter3_body)
 // pass converts the item's exact 64-bit sums to fp32 (one rounding) and adds them straight to row hash(gx, gy) of the level's
 // table gradient with fire-and-forget float atomics — the same number of memory-side atomic requests as the adds into the
 // fixed-point vertex grid they replace (one per non-zero vertex of the item's sub-grids), no fixed-point grid to clear, no
-// vertex_bwd_hash64 launch behind the kernel (10.7 us of a 396 us step).  What is given up: a vertex shared by several items (tile
-// borders; every vertex of the coarse levels, whose cells span several tiles) now receives one fp32 add per item instead of one
-// exact sum, so a table row is an fp32 sum of up to ~16 exactly rounded partial sums (was: one per vertex that hashes to it).
+// vertex-stage launch behind the kernel (round 4's vertex_bwd_hash64: 10.7 us of a 396 us step).  What is given up: a vertex
+// shared by several items (tile borders; every vertex of the coarse levels, whose cells span several tiles) now receives one
+// fp32 add per item instead of one exact sum, so a table row is an fp32 sum of up to ~16 exactly rounded partial sums (was:
+// one per vertex that hashes to it).
 template <bool L16, bool HDT = false>
 __global__ void __launch_bounds__(kTB)
 tiled_bwd_il_kernel(const float4* __restrict__ sorted, const int4* __restrict__ items, const int32_t* __restrict__ n_items,
@@ -1656,29 +1657,6 @@ dg64_to_float_kernel(const unsigned long long* __restrict__ dG64, float* __restr
   const int S = (int)(long long)dG64[nvals];
   const bool poisoned = dG64[nvals + 1] != 0ull;
   dG[e] = poisoned ? __int_as_float(0x7fc00000) : (float)((double)(long long)dG64[e] * ldexp(1.0, -S));
-}
-
-// dG64 -> table gradient, spatial-hash index source (= vertex_bwd_kernel<F, false> reading the fixed-point grid)
-template <int F>
-__global__ void __launch_bounds__(256)
-vertex_bwd_hash64_kernel(const unsigned long long* __restrict__ dG64, const int32_t* __restrict__ n_ls, float* __restrict__ dtables,
-                         int Ls, int64_t T, bool pow2, int64_t vtot) {
-  int l = 0, gw = n_ls[0] + 2;
-  int64_t goff = 0;
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  while (l + 1 < Ls && e >= goff + (int64_t)gw * gw) { goff += (int64_t)gw * gw; ++l; gw = n_ls[l] + 2; }
-  if (e - goff >= (int64_t)gw * gw) return;
-  const int i = (int)(e - goff);
-  const int gy = i / gw, gx = i - gy * gw;
-  const int S = (int)(long long)dG64[vtot * F];
-  const bool poisoned = dG64[vtot * F + 1] != 0ull;
-  float* r = dtables + ((int64_t)l * T + spatial_hash(gx, gy, T, pow2)) * F;
-#pragma unroll
-  for (int f = 0; f < F; ++f) {
-    const long long v = (long long)dG64[e * F + f];
-    if (poisoned) atomicAdd(r + f, __int_as_float(0x7fc00000));
-    else if (v != 0) atomicAdd(r + f, (float)((double)v * ldexp(1.0, -S)));
-  }
 }
 
 // HASHFUSE: the vertex stage backward of the spatial-hash index source rides along — the summed gradient of vertex (l, gx, gy)
@@ -2398,11 +2376,11 @@ extern "C" int gngf_encode_tiled_bwd(const float* sorted, const int32_t* items, 
         g64 ? log2_pixels : log2_chunk, nwork, ride, mride, g64, bride, hdt ? hash_dtables : nullptr, hash_T, hpow2);
     if (hdt) GNGF_RETURN_LAUNCH();
     if (g64) {
-      if (hash_dtables)
-        vertex_bwd_hash64_kernel<2><<<dim3((unsigned)ceil_div(vtot_h, 256)), dim3(256), 0, as_stream(stream)>>>(
-            g64, n_ls, hash_dtables, Ls, hash_T, hpow2, vtot_h);
-      else if (dG)        // (dG NULL: the caller's vertex stage reads the fixed-point grid itself — gngf_vertex_grid_bwd_sorted(dG64))
+      if (dG)        // (dG NULL: the caller's vertex stage reads the fixed-point grid itself — gngf_vertex_grid_bwd_sorted(dG64))
         dg64_to_float_kernel<<<dim3((unsigned)ceil_div(vtot_h * 2, 256)), dim3(256), 0, as_stream(stream)>>>(g64, dG, vtot_h * 2);
+      if (hash_dtables)   // (dG is set: checked above) the spatial-hash vertex stage on the converted grid, as gngf_vertex_grid_bwd
+        vertex_bwd_kernel<2, false, float><<<dim3((unsigned)ceil_div(vtot_h, 256)), dim3(256), 0, as_stream(stream)>>>(
+            nullptr, nullptr, nullptr, n_ls, dG, hash_dtables, nullptr, Ls, hash_T, 0, 0, 0, hpow2);
       GNGF_RETURN_LAUNCH();
     }
     if (hash_dtables)

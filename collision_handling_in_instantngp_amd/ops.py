@@ -20,9 +20,9 @@ _f32, _i32, _i64 = torch.float32, torch.int32, torch.int64
 
 # ------------------------------------------------------------------------------------------------ tuning: ONE frozen object
 # Every measured threshold and A/B switch of the dispatch lives in ops.TUNING (round 5; they were ~35 module globals).  The object is
-# frozen: a change replaces it as a whole — `ops.TUNING = dataclasses.replace(ops.TUNING, dg64=False)` — and, for the tests, tools
-# and `bench.py --set NAME=VALUE` written against the old names, `ops.DG64 = False` / `ops.DG64` still work (the module forwards
-# upper-case names of fields to the object).  The comments that explain each field stand where the mechanism is implemented
+# frozen: a change replaces it as a whole — `ops.TUNING = dataclasses.replace(ops.TUNING, bin_pipeline=False)` — and, for the tests,
+# tools and `bench.py --set NAME=VALUE` written against the old names, `ops.BIN_PIPELINE = False` / `ops.BIN_PIPELINE` still work
+# (the module forwards upper-case names of fields to the object).  The comments that explain each field stand where the mechanism is implemented
 # ("# TUNING.<name> (default ...)" lines below).  Which kernel chain a step takes is decided ONCE per forward pass from this
 # object, the plan and the model's state: StepConfig.choose().
 @_dc.dataclass(frozen=True)
@@ -59,13 +59,8 @@ class Tuning:
     bin_blocks_max: int = 128
     bin_pixels_per_block: int = 8192
     # ---- tiled form: which kernels (StepConfig.choose reads these)
-    two_launch_binning: bool = True           # count -> scatter with the scans riding inside (else four launches)
     fused_vertex_fwd: bool = True             # vertex stage forward inside the interleaved pixel stage's staging loop
     bin_pipeline: bool = True                 # an announced next batch is binned by riders of this step's pixel-stage launches
-    dg64: bool = True                         # interleaved backward: 64-bit fixed-point vertex grid fed by integer atomics
-    hash_vertex_fusion: bool = True           # hash source, single rank: no vertex-stage launch of its own
-    hash_direct_scatter: bool = True          # ... and no vertex grid at all: the pixel stage adds to the hashed table rows (round 5)
-    vertex_reads_dg64: bool = True            # slot-ordered vertex backward converts the fixed-point grid on the fly
     use_side_stream: bool = True              # False: helper-stream work in line on the current stream (measurement)
     # ---- decoder (csrc/decoder.hip)
     decoder_save_hidden: bool = True          # two-kernel path: hidden layers travel forward -> backward through HBM instead of being recomputed
@@ -1177,7 +1172,6 @@ class EncodePlan:
 
 # TUNING.bin_blocks_max (default 128)            — binning workgroups: more do not help (measured: tools/perf_bin.py, tools/perf_overlap.py)
 # TUNING.bin_pixels_per_block (default 8192)
-# TUNING.two_launch_binning (default True)     — count -> scatter (the scans ride inside the scatter launch) when the launch carries no gradient clear
 _BIN_WORKSPACES = {}
 
 
@@ -1244,7 +1238,7 @@ class TiledWorkspace:
                      ptr(self.tile_off), ptr(self.tile_item_base), ptr(self.items), ptr(self.n_items), ptr(self.sorted),
                      *_tab(tables), ptr(vert_idx), ptr(vert_w), ptr(n_ls), plan.n_ls_c, ptr(G), ptr(zero_dG), int(zero_dG_words), plan.Ls, F, T,
                      0 if vert_idx is None else vert_idx.shape[1], mode, vstride, 0 if vert_idx is None else vert_idx.shape[0],
-                     ptr(zero), 0 if zero is None else zero.numel(), ptr(_bin_workspace(dev, plan.ntiles, owner) if TUNING.two_launch_binning else None),
+                     ptr(zero), 0 if zero is None else zero.numel(), ptr(_bin_workspace(dev, plan.ntiles, owner)),
                      ptr(clear_rows if vert_idx is None else None, _f32, "clear_rows"), stream_ptr())
             except Exception:
                 # the count launch may have run without the scatter launch that puts the persistent counters back to zero: the
@@ -1331,22 +1325,18 @@ def tile_level_offsets(plan, device):
     return hit
 
 
-# TUNING.hash_vertex_fusion (default True)    — hash indexing, single rank: the vertex stage backward rides on the gather pass of the pixel stage
-
-
 # The kernel chain of one training step at the headline shape, as a string that changes whenever the chain does: PMC traffic
 # figures (profiles/traffic.json) are stamped with it and bench.py reports them only for the chain they were measured on.
 STEP_CHAIN_SIGNATURE = "r5: [bin_count_ride+bin_scatter2 | riders of the previous step] > tiled_fwd_il<SRC tables>(+count riders) > decoder_train > tiled_bwd_il(+scatter tasks, reduce, mse)<hash: HDT, table rows added by the store pass> [> vertex_bwd_sorted<FROM64> (vertex-table source)]"
 # TUNING.fused_vertex_fwd (default True)      — fp32 tables on the interleaved forward kernel: the vertex stage forward runs inside its staging loop
 # TUNING.bin_pipeline (default True)          — ... and an announced next batch (BinPipeline) is binned by riders of this step's pixel-stage launches
-# TUNING.dg64 (default True)                  — F = 2, <= 16 staged levels, bounded |genc|: 64-bit fixed-point vertex grid fed by global integer atomics
-# Round 5, spatial-hash source on a single rank (no exchange): the pixel-stage backward (level-interleaved AND generic kernels) adds
-# its items' exact sums — rounded to fp32 once per item and vertex — straight to the table-gradient rows hash(gx, gy): no vertex grid
-# (nothing to clear, nothing to convert), no vertex-stage launch behind the interleaved kernel (vertex_bwd_hash64: 10.7 us of the
-# 396 us hash step) and no partial images + gather pass behind the generic one (gather_partials: 121 / 245 us at the 4096^2 / 8192^2
-# shapes).  False: round 4's chains (fixed-point grid + vertex_bwd_hash64; partial images + gather_partials<HASHFUSE>).
-# TUNING.hash_direct_scatter (default True)
-# TUNING.vertex_reads_dg64 (default True)     — ... and the slot-ordered vertex backward converts it on the fly (False: dg64_to_float first)
+# F = 2, <= 16 staged levels, bounded |genc| (every source but the single-rank hash one below): the interleaved backward adds into a
+# 64-bit fixed-point vertex grid fed by global integer atomics; the slot-ordered vertex backward converts it on the fly (dg64_to_float
+# first where an exchange or d w needs the fp32 grid).
+# Spatial-hash source on a single rank (no exchange): the pixel-stage backward (level-interleaved AND generic kernels) adds its
+# items' exact sums — rounded to fp32 once per item and vertex — straight to the table-gradient rows hash(gx, gy): no vertex grid
+# (nothing to clear, nothing to convert), no vertex-stage launch behind the interleaved kernel (10.7 us of the 396 us hash step in
+# round 4) and no partial images + gather pass behind the generic one (gather_partials: 121 / 245 us at the 4096^2 / 8192^2 shapes).
 
 
 PIXEL_BWD_TRACE = None       # tests: a list that receives one record per pixel-stage backward launch (which chain ran)
@@ -1446,9 +1436,9 @@ class StepConfig:
     with the gradient buffer, the model's data-parallel state and ops.TUNING), recorded on the model (`net.dp.step_config`), in
     ops.STEP_TRACE and in bench.py's line (`config.step_config`).  forward() and backward() read it instead of re-deriving it.
     What only the backward pass can know (did a bound on |d enc| arrive? is this a second backward through the same graph?) can
-    DEMOTE the planned chain to the general one (partial images + gather pass, zeroed allocations); that is traced too
-    ("pixel_bwd" records of PIXEL_BWD_TRACE).  tests/test_step_config_cpu.py enumerates the reachable configurations and names
-    the GPU parity test that runs each."""
+    DEMOTE the planned chain to the general one (partial images + gather pass, zeroed allocations): EncodeFunction.backward decides
+    those fallbacks in one place, and they are traced too (PIXEL_BWD_TRACE records, the "table_grad" record of STEP_TRACE).
+    tests/test_step_config_cpu.py enumerates the reachable configurations and names the GPU parity test that runs each."""
     source: str            # "hash" | "vertex_table"
     staged: int            # levels in the tiled form (plan.Ls); 0: direct form only
     direct: int            # levels in the direct form
@@ -1486,16 +1476,15 @@ class StepConfig:
             return StepConfig(src, 0, L, "none", "none", "none", "none", "alloc" if needs_grad else "none", "none",
                               "bucketed_or_atomics" if (needs_grad and nd > 0) else "none", False)
         il_f, il_b = plan.interleaved(backward=False), plan.interleaved(backward=True)
-        fused = bool(t.fused_vertex_fwd and t.two_launch_binning and have_reserve_ws and fp32_tables and F == 2 and il_f)
+        fused = bool(t.fused_vertex_fwd and have_reserve_ws and fp32_tables and F == 2 and il_f)
         if needs_grad and (L * T * F) % 4 != 0:
             fused = False                                    # (the one-block gradient allocation wants whole 16-byte vectors)
         if not needs_grad:
             vf0 = "fused" if (fused or (t.fused_vertex_fwd and mode == MODE_HASH and not il_f)) else "riders"
             return StepConfig(src, plan.Ls, nd, "pipeline" if fused else "prepare", vf0,
                               "interleaved" if il_f else "generic", "none", "none", "none", "none", bool(exchange))
-        direct_hash = bool(t.hash_direct_scatter and t.hash_vertex_fusion and mode == MODE_HASH and not exchange)
-        use64 = bool(t.dg64 and F == 2 and plan.Ls <= 16 and il_b)
-        sink = "table_rows" if direct_hash else ("dG64" if use64 else "fp32_grid")
+        use64 = F == 2 and plan.Ls <= 16 and il_b
+        sink = "table_rows" if (mode == MODE_HASH and not exchange) else ("dG64" if use64 else "fp32_grid")
         if fused:
             return StepConfig(src, plan.Ls, nd, "pipeline", "fused", "interleaved", sink, "block", "decoder" if link_defer_zero else "riders",
                               "bucketed_or_atomics" if nd > 0 else "none", bool(exchange))
@@ -1509,6 +1498,17 @@ class StepConfig:
         return StepConfig(src, plan.Ls, nd, "prepare", vf, "interleaved" if il_b else "generic", sink,
                           "persist" if persist else "alloc", "rows" if persist else ("decoder" if link_defer_zero else "riders"),
                           "bucketed_write" if fresh else ("bucketed_or_atomics" if nd > 0 else "none"), bool(exchange))
+
+
+@_dc.dataclass
+class _BackwardBuffers:
+    """What a forward pass of EncodeFunction leaves for the FIRST backward pass through its graph (ctx.buffers, taken once: a
+    second backward finds None and takes zeroed allocations of its own).  Which chain they serve is ctx.step_config."""
+    dgrid: object = None            # vertex-grid gradient of sink "dG64" (int64) / "fp32_grid" (fp32), cleared; None: "table_rows"
+    dtables: object = None          # table gradient of table_grad "block" / "alloc"; None: "persist" (the backward takes the buffer)
+    zbuf: object = None             # the buffer whose clear forward arranged: riders of the binning, or the decoder (link.zero_request)
+    persist_cleared: object = None  # "persist": the buffer generation whose staged levels' rows the binning's riders cleared
+    next_bin: object = None         # (workspace, gngf_bin_job, coordinates, BinPipeline): the next batch, binned by the backward's launch
 
 
 class EncodeFunction(torch.autograd.Function):
@@ -1529,16 +1529,11 @@ class EncodeFunction(torch.autograd.Function):
         ws = None
         if vert_idx is not None and order is None and plan.Ls > 0 and P > 0 and ctx.needs_input_grad[3]:
             order = slot_order(vert_idx, plan.n_ls_host[:plan.Ls], vstride)
-        pre = None
-        ctx.next_bin = None
-        ctx.fresh_direct = False
-        ctx.direct_hash = False
-        ctx.persist = False
-        ctx.persist_cleared = None
+        buf = None
         clear_now = None
         dev = tables.device
         tiled = plan.Ls > 0 and P > 0
-        pws = _bin_workspace(dev, plan.ntiles, dp, kind="reserve") if (tiled and TUNING.two_launch_binning and TUNING.fused_vertex_fwd) else None
+        pws = _bin_workspace(dev, plan.ntiles, dp, kind="reserve") if (tiled and TUNING.fused_vertex_fwd) else None
         # ONE decision per pass (see StepConfig): which kernels, which buffers, who clears them
         sc = ctx.step_config = StepConfig.choose(
             plan, L, T, F, P, mode, tables.dtype == _f32, bool(ctx.needs_input_grad[3]),
@@ -1557,45 +1552,39 @@ class EncodeFunction(torch.autograd.Function):
             # launches carried it (BinPipeline)
             fused = sc.vertex_fwd == "fused" and sc.binning == "pipeline"      # (the interleaved kernel's own binning: two launches or riders)
             use64 = sc.grad_sink == "dG64"
-            big = None
             if ctx.needs_input_grad[3]:
                 # grad_sink "dG64" (F = 2, <= 16 staged levels: the level-interleaved kernels): the pixel stage of the backward adds
                 # its exact fixed-point sums straight into a 64-bit vertex grid (cleared here; + scale and poison words), no gather
                 # pass; "fp32_grid": the generic kernels (e.g. the 4096^2 shape, whose interleaved image exceeds the LDS) accumulate
                 # into a ZEROED fp32 grid; "table_rows" (hash source, single rank): no vertex-grid gradient at all — the pixel stage
                 # adds to the table gradient itself
-                ctx.direct_hash = sc.grad_sink == "table_rows"
+                ng = 0 if sc.grad_sink == "table_rows" else ((plan.vtot * F + 2) * 2 if use64 else plan.vtot * F)
                 nt = tables.numel()
                 if fused:
                     # ONE allocation [table gradient | vertex-grid gradient]: whoever clears the table gradient — the fused
                     # training decoder between its MFMAs, or rider workgroups of the count launch — clears both
-                    ng = 0 if ctx.direct_hash else ((plan.vtot * F + 2) * 2 if use64 else plan.vtot * F)
                     big = torch.empty((nt + ((ng + 3) & ~3),), dtype=_f32, device=dev)
-                    dgrid = None if ctx.direct_hash else (big[nt:nt + ng].view(_i64) if use64 else big[nt:nt + ng].view(plan.vtot, F))
-                    pre = [big[:nt].view(tables.shape), dgrid, big, big]
+                    dgrid = None if ng == 0 else (big[nt:nt + ng].view(_i64) if use64 else big[nt:nt + ng].view(plan.vtot, F))
+                    buf = _BackwardBuffers(dgrid, big[:nt].view(tables.shape), zbuf=big)
                 else:
-                    dgrid = None if ctx.direct_hash else (torch.empty((plan.vtot * F + 2,), dtype=_i64, device=dev) if use64
-                                                          else torch.empty((plan.vtot, F), dtype=_f32, device=dev))
-                    # direct_bwd "bucketed_write": direct levels whose backward WRITES every row are left out of the clear
-                    fresh = sc.direct_bwd == "bucketed_write"
-                    ctx.fresh_direct = fresh
+                    dgrid = None if ng == 0 else (torch.empty((plan.vtot * F + 2,), dtype=_i64, device=dev) if use64
+                                                  else torch.empty((plan.vtot, F), dtype=_f32, device=dev))
                     # table_grad "persist": with a step-to-step buffer there is no dense clear at all (the backward takes the buffer,
                     # or a zeroed allocation when the buffer is in use) — not for small tables where the training decoder clears
                     # the buffer between its MFMAs at next to no cost (at the 4096^2 shape that hidden clear of 448 MB costs the
                     # decoder 36 us — a draw against a sparse-clear LAUNCH of 7.3 M rows, a loss against the same clear riding on
                     # the vertex riders: tools/ab_persist_cfg4.sh)
-                    ctx.persist = sc.table_grad == "persist"
-                    if ctx.persist:
-                        pre = [None, dgrid, None, None]
+                    if sc.table_grad == "persist":
                         # the rows the staged levels can touch are cleared by the vertex riders of the binning launch, if the
                         # buffer is free now (else the backward pass clears them, or takes an allocation of its own)
                         clear_now = _persistent_peek(dp, tables)
-                        ctx.persist_cleared = dp.persist_gen if clear_now is not None else None
+                        buf = _BackwardBuffers(dgrid, persist_cleared=dp.persist_gen if clear_now is not None else None)
                     else:
+                        # direct_bwd "bucketed_write": direct levels whose backward WRITES every row are left out of the clear
                         dt_ = torch.empty(tables.shape, dtype=_f32, device=dev)
-                        pre = [dt_, dgrid, None, dt_[:plan.Ls] if fresh else dt_]
+                        buf = _BackwardBuffers(dgrid, dt_, zbuf=dt_[:plan.Ls] if sc.direct_bwd == "bucketed_write" else dt_)
                 tile_level_offsets(plan, dev)        # cached; built here so that no backward (or graph capture) uploads it
-            zbuf = None if pre is None else pre[3]
+            zbuf = None if buf is None else buf.zbuf
             defer = zbuf is not None and link is not None and link.defer_zero and zbuf.numel() % 4 == 0
             if defer:
                 link.zero_request = zbuf
@@ -1623,7 +1612,7 @@ class EncodeFunction(torch.autograd.Function):
                     ws_next = nws if nws is not None else TiledWorkspace(plan, nx, launch=False)
                     job_next = _bin_job(ws_next, plan, nx, pws)
                     pipe.pending = ws_next
-                    ctx.next_bin = (ws_next, job_next, nx, pipe)
+                    buf.next_bin = (ws_next, job_next, nx, pipe)
                 call("gngf_encode_tiled_fwd_fused", ptr(ws.sorted), ptr(ws.items), ptr(ws.n_items), plan.max_items, ptr(n_ls), plan.n_ls_c,
                      *_tab(tables), ptr(vert_idx), ptr(vert_w), ptr(enc), L, plan.Ls, F, T, K, mode, vstride, NV, plan.tile_shift,
                      plan.lds_bytes, _ct.byref(job_next) if job_next is not None else None, stream_ptr())
@@ -1632,9 +1621,10 @@ class EncodeFunction(torch.autograd.Function):
                 # and the clears ride on the binning kernels as extra workgroups: ops.TiledWorkspace)
                 gather = sc.vertex_fwd == "fused"             # hash source on the generic kernels: no vertex grid (riders only clear)
                 G = None if gather else torch.empty((plan.vtot, F), dtype=_f32, device=dev)
+                dgrid = None if buf is None else buf.dgrid
                 ws = TiledWorkspace(plan, xy, vertex=(tables, vert_idx, vert_w, n_ls, vstride, G),
-                                    zero_dG=(pre[1].view(_f32) if pre[1].dtype == _i64 else pre[1]) if (pre and pre[1] is not None) else None,
-                                    zero=(pre[3] if (pre and pre[3] is not None and not defer) else None),
+                                    zero_dG=None if dgrid is None else (dgrid.view(_f32) if use64 else dgrid),
+                                    zero=(zbuf if (zbuf is not None and not defer) else None),
                                     zero_dG_words=(2 if use64 else 1), owner=dp, clear_rows=clear_now)
                 if gather:
                     call("gngf_encode_tiled_fwd_fused", ptr(ws.sorted), ptr(ws.items), ptr(ws.n_items), plan.max_items, ptr(n_ls), plan.n_ls_c,
@@ -1649,13 +1639,14 @@ class EncodeFunction(torch.autograd.Function):
                  ptr(ws.sorted if (TUNING.direct_fwd_tile_order and ws is not None) else None, _f32, "pixel_order"), stream_ptr())
         ctx.save_for_backward(xy, n_ls, tables, vert_idx, vert_w, order)
         ctx.cfg = (P, L, F, T, K, mode, vstride, NV, plan, ws)
-        ctx.pre = pre                                           # zero-filled (dtables, dG), consumed by the first backward
+        ctx.buffers = buf                                       # consumed by the first backward
         return enc
 
     @staticmethod
     def backward(ctx, genc):
         xy, n_ls, tables, vert_idx, vert_w, order = ctx.saved_tensors
         P, L, F, T, K, mode, vstride, NV, plan, ws = ctx.cfg
+        sc = ctx.step_config
         genc = _c(genc)
         dp, link, sink = ctx.dp, ctx.link, ctx.sink
         absmax = link.take_absmax(genc) if link is not None else None
@@ -1666,41 +1657,47 @@ class EncodeFunction(torch.autograd.Function):
             dp.deferred = None
         exchange = dp.exchange if dp is not None else None
         NONE = (None,) * 5                                      # (order, dp, link, sink) + vstride: no gradients
-        pre, ctx.pre = ctx.pre, None                            # a second backward (retain_graph) allocates fresh buffers
-        zbuf = None if not pre else pre[3]
-        fresh_direct = bool(pre) and getattr(ctx, "fresh_direct", False)        # (a second backward gets a zeroed buffer: nothing is fresh)
-        if zbuf is not None and link is not None and link.zero_request is zbuf:
+        buf, ctx.buffers = ctx.buffers, None                    # a second backward (retain_graph) allocates fresh buffers
+        if buf is not None and buf.zbuf is not None and link is not None and link.zero_request is buf.zbuf:
             link.zero_request = None                            # the decoder that was to clear the buffer did not run: clear it here
-            zbuf.zero_()
-        next_bin, ctx.next_bin = getattr(ctx, "next_bin", None), None
-        dtables = pre[0] if pre else None
-        if dtables is None and pre and getattr(ctx, "persist", False):
+            buf.zbuf.zero_()
+        # The chain is the forward pass's StepConfig.  It departs from it only here, for what the forward pass could not know:
+        #   1. no bound on |d enc| arrived (the per-item scales of the fixed-point grid need one): "dG64" -> fp32 grid
+        #   2. the interleaved kernels were switched off since the forward pass (gngf_set_tiled_interleaved): "dG64" -> fp32 grid
+        #   3. a second backward through the same graph (no buffers left): zeroed allocations; hash source on a single rank: the
+        #      gather pass with the hash fused in, on a vertex grid allocated here
+        #   4. the step-to-step gradient buffer is still held (table_grad "persist"): a zeroed allocation
+        grad_sink, dgrid = (sc.grad_sink, buf.dgrid) if buf is not None else ("fp32_grid", None)
+        if grad_sink == "dG64" and (absmax is None or not plan.interleaved(backward=True)):
+            grad_sink, dgrid = "fp32_grid", None
+        dtables = None if buf is None else buf.dtables
+        if buf is not None and sc.table_grad == "persist":
             # staged levels' rows cleared (by this pass's forward, or now); the direct levels will be written
-            dtables = _persistent_grad(dp, tables, plan, n_ls, getattr(ctx, "persist_cleared", None))
+            dtables = _persistent_grad(dp, tables, plan, n_ls, buf.persist_cleared)
         _trace("table_grad", source=("persist" if (dtables is not None and dp is not None and dtables is getattr(dp, "persist_grad", None))
                                      else ("forward_alloc" if dtables is not None else "zeroed_alloc")))
+        # direct_bwd "bucketed_write": the direct levels of the buffer the forward pass left hold nothing yet (a zeroed one is not fresh)
+        fresh_direct = dtables is not None and sc.direct_bwd == "bucketed_write"
         if dtables is None:
             dtables = _grad_buffer(tables)                      # a zeroed allocation of this pass's own
-            fresh_direct = False
         dvw = torch.zeros_like(vert_w) if (vert_w is not None and ctx.needs_input_grad[5]) else None
         if plan.Ls > 0 and P > 0:
-            dG64 = pre[1] if (pre and pre[1] is not None and pre[1].dtype == _i64) else None
-            if dG64 is not None and absmax is None:            # no bound on |genc| from its producer: the per-item scales need the fp32 path
-                dG64 = None
-            if dG64 is not None and not plan.interleaved(backward=True):
-                dG64 = None                                     # gngf_set_tiled_interleaved changed since the forward pass: fp32 path
-            fuse = (dtables, T) if (TUNING.hash_vertex_fusion and vert_idx is None and exchange is None) else None
-            # the forward pass planned for it (no vertex-grid gradient was allocated) and the conditions still hold: the pixel stage
-            # — level-interleaved or generic kernel, with or without a bound on |d enc| — adds to the table gradient itself.
-            # Otherwise (a second backward pass through the same graph): partial images + gather pass with the hash fused in, on a
-            # vertex grid allocated here
-            direct_hash = bool(getattr(ctx, "direct_hash", False) and pre and fuse is not None)
+            # hash source, single rank: the vertex stage backward rides on the pixel stage (its store pass or its gather pass)
+            fuse = (dtables, T) if (vert_idx is None and exchange is None) else None
+            # sink "table_rows": the pixel stage — level-interleaved or generic kernel, with or without a bound on |d enc| — adds
+            # to the table gradient itself
+            direct_hash = grad_sink == "table_rows" and fuse is not None
+            dG64 = dgrid if grad_sink == "dG64" else None
             # vertex-table source in slot order, single rank, no d w: the vertex stage reads the fixed-point grid itself (no
             # fp32 copy of the vertex-grid gradient, no conversion launch)
-            direct64 = (dG64 is not None and TUNING.vertex_reads_dg64 and vert_idx is not None and order is not None and exchange is None
-                        and dvw is None)
-            dG = None if (direct64 or direct_hash) else (pre[1] if (pre and pre[1] is not None and pre[1].dtype == _f32) else
-                                                         (torch.empty if dG64 is not None else torch.zeros)((plan.vtot, F), dtype=_f32, device=tables.device))
+            direct64 = dG64 is not None and vert_idx is not None and order is not None and exchange is None and dvw is None
+            if direct64 or direct_hash:
+                dG = None
+            elif dG64 is None and dgrid is not None:
+                dG = dgrid                                      # the forward pass's zeroed fp32 grid
+            else:                                               # (dg64_to_float writes every element of it)
+                dG = (torch.empty if dG64 is not None else torch.zeros)((plan.vtot, F), dtype=_f32, device=tables.device)
+            next_bin = None if buf is None else buf.next_bin
             job_next = None
             if next_bin is not None and plan.interleaved(backward=True):
                 job_next = next_bin[1]

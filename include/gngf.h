@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNGF_ABI_VERSION 13
+#define GNGF_ABI_VERSION 14
 #define GNGF_MAX_LEVELS 32
 #define GNGF_MAX_TOPK 32
 
@@ -218,11 +218,13 @@ int gngf_encode_tiled_bwd(const float* sorted, const int32_t* items, const int32
  * this launch writes (the vertex-grid gradient and the ridden decoder gradients) is NaN — checked on the device, no sync.
  * hash_dtables (optional; (L, hash_T, F) fp32 gradient buffer): spatial-hash index source on a single rank — the gather pass
  * adds every vertex's gradient straight to row _fast_hash(gx, gy) of the level's table gradient (= gngf_vertex_grid_bwd in hash
- * mode for levels [0, Ls)) and leaves dG unwritten: one launch and one round trip of dG less.
+ * mode for levels [0, Ls)) and leaves dG unwritten: one launch and one round trip of dG less.  With dG = dG64 = NULL the work
+ * items add their sums to those rows themselves (no vertex grid, no gather pass).
  * dG64 (optional; (vtot * F + 2) 64-bit words, ZERO on entry — gngf_encode_tiled_prepare clears it with dG_zero_words = 2) with
  * log2_pixels >= ceil(log2(P)) and a bound on |genc| (genc_absmax): the work items add their exact 64-bit fixed-point sums
  * straight into this vertex grid with global integer atomics (no partial images, no gather pass; bitwise reproducible), and
- * the launch ends with the conversion to dG (fp32) or — with hash_dtables — with the hash-source vertex stage reading dG64.
+ * the launch ends with the conversion to dG (fp32) or — with hash_dtables — with the conversion and the hash-source vertex
+ * stage reading dG.
  * Used by the interleaved kernels (F = 2, <= 16 staged levels); ignored otherwise.
  * mse_* (optional, mse_pred NULL = none): likewise gngf_mse_fwd(mse_pred, mse_label, mse_loss, mse_workspace, mse_n) — the
  * VALUE of the pixel loss, which no kernel of the step reads. */
@@ -244,11 +246,6 @@ int gngf_vertex_grid_bwd_sorted(const void* tables, int feat_dtype, const int32_
  *      products: |error| <= 3 * 2^-18 |a b| per product (the HashProbDistribution's dW / dh, contractions of >= 4096 terms)
  *   17 the round-4 kernel: every wave splits the fragments it reads (kept for A/B; same numbers as 1) */
 int gngf_set_gemm_split_bf16(int mode);
-/* The same switch for the fused decoder (gngf_decoder_fwd / gngf_decoder_bwd) at in_dim 32 or 64: exact three-way bf16
- * split of every operand, six cross products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  While on, the hidden-layer
- * buffer is neither written by the forward nor read by the backward (the backward recomputes the two layers).  Process-wide;
- * returns the previous setting. */
-int gngf_set_decoder_split_bf16(int on);
 /* gngf_decoder_bwd at in_dim == 32 with the saved hidden layers: 1 (default) = hybrid kernel — the two products with the pixel
  * on the lane (dh1 = W1^T dz2, d enc = W0^T dz1) on the bf16 pipe with the exact three-way split, the weight-gradient products
  * on the fp32 pipe; 0 = everything on the fp32 pipe.  Process-wide; returns the previous setting. */

@@ -56,8 +56,8 @@ def _oracle_step(x, y, n_ls, tables, dw, db, vidx=None, vw=None, vstride=0, genc
 @pytest.mark.parametrize("mode", ["hash", "gngf_frozen"])
 def test_bench_step_at_full_size_matches_the_oracle(mode):
     """VERDICT r3 item 2(b).  The model, the batch and the step are built by bench.py's own functions; the graph is replayed twice
-    (the second replay is what a timed step is).  The encoder runs binning -> tiled_fwd_il -> decoder_train -> tiled_bwd_il (dG64)
-    -> vertex_bwd_hash64 | vertex_bwd_sorted<FROM64>."""
+    (the second replay is what a timed step is).  The encoder runs binning -> tiled_fwd_il -> decoder_train -> tiled_bwd_il (hash:
+    the table rows added by its store pass | gngf_frozen: dG64 -> vertex_bwd_sorted<FROM64>)."""
     import bench
     from collision_handling_in_instantngp_amd import models, ops, train
     cfg = bench.MODES[mode]

@@ -317,20 +317,16 @@ def test_decoder_saved_hidden_equals_recompute(ops, P, in_dim, leaky):
         np.testing.assert_array_equal(a, b)
 
 
-@pytest.mark.parametrize("variant", ["hybrid", "split"])
+@pytest.mark.parametrize("variant", ["hybrid"])
 @pytest.mark.parametrize("P,leaky", [(1000, False), (128 * 300 + 77, True)])
 def test_bf16_split_decoder_kernels_are_as_accurate_as_the_fp32_ones(ops, P, leaky, variant):
     """The decoder products moved to v_mfma_f32_32x32x16_bf16 with every operand split exactly into three bf16 terms:
     "hybrid" (the default backward at 32 input features: dh1 and d enc on the bf16 pipe, weight gradients on the fp32 pipe,
-    csrc/decoder.hip) and "split" (gngf_set_decoder_split_bf16(1): everything, csrc/decoder_split.inc).  Against a float64
-    evaluation the error must not exceed twice that of the all-fp32 kernels (+ 1e-7 absolute on rgb); a hidden unit whose
-    pre-activation is within rounding of 0 may switch sides, which changes that pixel's gradient — hence the 99.9 % quantile
-    for d enc and the looser bound on the summed gradients."""
+    csrc/decoder.hip with the split helpers of csrc/decoder_split.inc).  Against a float64 evaluation the error must not exceed
+    twice that of the all-fp32 kernels (+ 1e-7 absolute on rgb); a hidden unit whose pre-activation is within rounding of 0 may
+    switch sides, which changes that pixel's gradient — hence the 99.9 % quantile for d enc and the looser bound on the summed
+    gradients."""
     from collision_handling_in_instantngp_amd import _lib
-    if variant == "split":
-        prev = _lib.query("gngf_set_decoder_split_bf16", 0)
-        if prev < 0:
-            pytest.skip("library built without the all-bf16 decoder kernels (make SPLIT=1 builds them)")
     rng = np.random.default_rng(P)
     x = (0.5 * rng.standard_normal((P, 32))).astype(np.float32)
     dims = [32, 64, 64, 3]
@@ -347,7 +343,6 @@ def test_bf16_split_decoder_kernels_are_as_accurate_as_the_fp32_ones(ops, P, lea
     want = [y64.detach(), x64.grad] + [p.grad for p in p64]
     errs = []
     for which in ("fp32", variant):
-        prev = _lib.query("gngf_set_decoder_split_bf16", 1 if which == "split" else 0) if variant == "split" else 0
         prev_h = _lib.query("gngf_set_decoder_bwd_hybrid", 1 if which == "hybrid" else 0)
         try:
             xt = t(x).requires_grad_()
@@ -356,8 +351,6 @@ def test_bf16_split_decoder_kernels_are_as_accurate_as_the_fp32_ones(ops, P, lea
             y.backward(t(dy))
             torch.cuda.synchronize()
         finally:
-            if variant == "split":
-                _lib.query("gngf_set_decoder_split_bf16", prev)
             _lib.query("gngf_set_decoder_bwd_hybrid", prev_h)
         got = [y.detach(), xt.grad] + [p.grad for p in params]
         e = [float((got[0].double() - want[0]).abs().max())]

@@ -315,7 +315,7 @@ def test_macaw_hash_step_at_headline_shape_matches_reference(golden, fused_train
             _lib.PROFILE = None
         assert ("gngf_decoder_train" in names) == fused_train, names
         assert ("gngf_encode_tiled_bwd" in names) == (encode_path.path == "tiled"), names
-        encode_path.assert_chain()      # "tiled": tiled_bwd_il -> dG64 -> vertex_bwd_hash64, the hash mode's chain in bench.py
+        encode_path.assert_chain()      # "tiled": tiled_bwd_il adding to the table rows itself, the hash mode's chain in bench.py
         ic = idx.cpu()
         chk = np.array([int(ic.sum()), int((ic * torch.arange(1, 4097)[:, None, None]).sum() % (2 ** 61 - 1))], dtype=np.int64)
         assert np.array_equal(chk, g["idx_checksum"])                            # index work: bit-exact

@@ -86,10 +86,10 @@ def test_choose_is_a_pure_function_of_its_arguments_and_the_tuning_object():
         a.grad_sink = "dG64"
     prev = ops.TUNING
     try:
-        ops.HASH_DIRECT_SCATTER = False                    # (the old upper-case names forward to the frozen object)
-        assert ops.TUNING is not prev and ops.TUNING.hash_direct_scatter is False
+        ops.FUSED_VERTEX_FWD = False                       # (the old upper-case names forward to the frozen object)
+        assert ops.TUNING is not prev and ops.TUNING.fused_vertex_fwd is False
         c = ops.StepConfig.choose(*args)
-        assert c.grad_sink == "dG64" and c != a
+        assert c.vertex_fwd == "riders" and c.binning == "prepare" and c != a
     finally:
         ops.TUNING = prev
     assert ops.StepConfig.choose(*args) == a
