@@ -87,8 +87,10 @@ SIGNATURES = {
     "gngf_distinct_slot_counts": [_P, _L, _I, _I, _I, _L, _P, _P, _P],
     "gngf_mark_batch_slots": [_P, _P, _L, _I, _P, _I, _L, _I, _L, _P, _P, _P],
     "gngf_count_slot_bits": [_P, _I, _I, _L, _P, _P],
+    "gngf_mark_reachable_rows": [_P, _P, _I, _P, _I, _L, _I, _L, _P, _P],
     "gngf_adam_block_elems": [],
     "gngf_adam_step": [_P, _I, _L, _P, _P, _P, _I, _F, _F, _F, _F, _P],
+    "gngf_adam_step_masked": [_P, _I, _L, _P, _P, _P, _I, _F, _F, _F, _F, _P, _P],
 }
 
 ABI_VERSION = 14

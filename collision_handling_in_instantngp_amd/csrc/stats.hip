@@ -100,9 +100,60 @@ touched_slots_kernel(const uint32_t* __restrict__ touched, int64_t vwords, const
   }
 }
 
+// ---- the rows a model can EVER address (gngf_mark_reachable_rows): level l reads and writes the rows of its vertices
+// 0 <= gx, gy <= N_l + 1 only (coordinates in [0,1]^2; the corners of weight 0 at N_l + 1 included) — hash(gx, gy), or the K
+// rows of the per-vertex table.  A set that depends on the level resolutions (and the frozen table), not on any batch.  One
+// lane per (level, vertex), laid out as clear_hashed_rows_kernel (csrc/encode_bucket.hip).
+__global__ void __launch_bounds__(256)
+reachable_rows_kernel(const int32_t* __restrict__ n_ls, int L, const int32_t* __restrict__ vert_idx, int K, int64_t T, bool pow2,
+                      int vstride, int64_t NV, uint32_t* __restrict__ rowmask, int64_t words) {
+  int l = 0, gw = n_ls[0] + 2;
+  int64_t goff = 0;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  while (l + 1 < L && e >= goff + (int64_t)gw * gw) { goff += (int64_t)gw * gw; ++l; gw = n_ls[l] + 2; }
+  if (e - goff >= (int64_t)gw * gw) return;
+  const int i = (int)(e - goff);
+  const int gy = i / gw, gx = i - gy * gw;
+  uint32_t* row = rowmask + (int64_t)l * words;
+  if (!vert_idx) {
+    const int64_t slot = spatial_hash(gx, gy, T, pow2);
+    const uint32_t bit = 1u << (slot & 31);
+    if (!(__atomic_load_n(row + (slot >> 5), __ATOMIC_RELAXED) & bit)) atomicOr(row + (slot >> 5), bit);
+    return;
+  }
+  const int64_t vid = (int64_t)gy * vstride + gx;
+  if (gx >= vstride || vid >= NV) return;                 // outside the table: not a vertex of it
+  for (int k = 0; k < K; ++k) {
+    const int64_t slot = vert_idx[vid * K + k];
+    if (slot < 0 || slot >= T) continue;
+    const uint32_t bit = 1u << (slot & 31);
+    if (!(__atomic_load_n(row + (slot >> 5), __ATOMIC_RELAXED) & bit)) atomicOr(row + (slot >> 5), bit);
+  }
+}
+
 }  // namespace gngf
 
 using namespace gngf;
+
+// ORs into `rowmask` ((L, ceil(T / 32)) words = gngf_slot_bitmap_words(L, 1, T); never cleared here: the caller zero-fills it
+// once) the rows level l can address, for every vertex 0 <= gx, gy <= N_l + 1: row spatial_hash(gx, gy) when vert_idx == NULL
+// (K = 1), else the K rows vert_idx[(gy * vstride + gx) * K + k] (vertices with gx >= vstride or beyond NV are not in the
+// table and are skipped).  n_ls: device, n_ls_host: the same L values on the host (they size the launch).  A superset of the
+// rows that can receive a non-zero gradient as long as coordinates lie in [0,1]^2.
+extern "C" int gngf_mark_reachable_rows(const int32_t* n_ls, const int32_t* n_ls_host, int L, const int32_t* vert_idx, int K,
+                                        int64_t T, int vstride, int64_t NV, uint32_t* rowmask, void* stream) {
+  GNGF_CHECK_ARG(L > 0 && L <= GNGF_MAX_LEVELS && K > 0 && K <= GNGF_MAX_TOPK && T > 0 && n_ls && n_ls_host && rowmask);
+  GNGF_CHECK_ARG(vert_idx ? (vstride > 0 && NV > 0) : K == 1);
+  int64_t total = 0;
+  for (int l = 0; l < L; ++l) {
+    GNGF_CHECK_ARG(n_ls_host[l] >= 0 && n_ls_host[l] < (1 << 24));
+    total += (int64_t)(n_ls_host[l] + 2) * (n_ls_host[l] + 2);
+  }
+  GNGF_CHECK_ARG(ceil_div(total, 256) < INT32_MAX);
+  reachable_rows_kernel<<<dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(stream)>>>(
+      n_ls, L, vert_idx, K, T, (T & (T - 1)) == 0, vstride, NV, rowmask, (T + 31) / 32);
+  GNGF_RETURN_LAUNCH();
+}
 
 // Marks, into `bitmap` (gngf_slot_bitmap_words(L, K, T) words; ACCUMULATED — the caller clears it once per epoch), the table
 // slots the batch `xy` uses: vert_idx (NV,K) int32 per-vertex table with vid = gy * vstride + gx, or NULL for the spatial hash

@@ -252,6 +252,7 @@ class GeneralNeuralGaugeFields(nn.Module):
         self._last_link = None             # ops.StepLink of the most recent forward pass
         self.track_collisions = False      # every forward pass also marks the table slots its batch uses (start_collision_tracking)
         self._slot_maps = None             # (slot bit maps (K|1, L, T bits), touched-vertex workspace)
+        self._row_map = None               # reachable_rows(): (L, ceil(T/32)) int32 bit map, allocated once, only ever gains bits
         self.to(device)
 
     # ------------------------------------------------------------------ helpers
@@ -333,7 +334,58 @@ class GeneralNeuralGaugeFields(nn.Module):
             tv, ti, _, _ = ops.HpdVertexFunction.apply(NV, vstride, self._topk_k, None, False, HPD_CHUNK_BYTES, None, *params)
             w = ops.BlendFunction.apply(tv, blend_code)
             self._frozen_table = (key, tv, ti, w, vstride, NV, ops.slot_order(ti, self._n_ls_host, vstride))
+            if self._row_map is not None:
+                self._mark_reachable_rows(ti, vstride, NV)     # OR: the map covers every table used since it exists
         return self._frozen_table[1:]
+
+    # ------------------------------------------------------------------ the rows the model can address at all
+    @torch.no_grad()
+    def _mark_reachable_rows(self, vert_idx, vstride, NV):
+        import ctypes
+        from ._lib import call, ptr, stream_ptr
+        L = self._num_levels
+        dev = self._row_map.device
+        host = (ctypes.c_int32 * L)(*self._n_ls_host)
+        K = 1 if vert_idx is None else int(vert_idx.shape[1])
+        call("gngf_mark_reachable_rows", ptr(self._n_ls_flat(dev), torch.int32), host, L, ptr(vert_idx, torch.int32), K,
+             self._hash_table_size, int(vstride), int(NV), ptr(self._row_map), stream_ptr())
+
+    def reachable_rows(self):
+        """(L, ceil(T/32)) int32 device tensor: bit (row & 31) of word [l, row >> 5] is set for every table row level l can
+        address at all — hash(gx, gy), or the K rows of the frozen HPD's per-vertex table, over the vertices 0 <= gx, gy <=
+        N_l + 1 (csrc/stats.hip: gngf_mark_reachable_rows).  Every other row never receives a gradient, which is what
+        train.get_optimizer(..., skip_unreachable_rows=True) relies on.  ONE tensor per model: allocated at the first call,
+        never cleared, its address stable (a captured step keeps it); a frozen table rebuilt after the HPD's weights changed
+        ORs its rows in, so the map covers every table used since the first call.
+        PRECONDITION: coordinates lie in [0, 1]^2 (as the step-to-step gradient buffer, gngf_clear_hashed_rows, assumes).
+        None when no such fixed set exists: a trainable HPD (the table changes every step), a frozen HPD whose forward pass
+        does not run on the cached table (dense or batch-mean distributions asked for), should_batchnorm_data (vertices
+        leave the grid; GNGF indexing then takes the per-instance path)."""
+        if should_batchnorm_data:
+            return None
+        frozen = None
+        if not self._hash_mode:
+            cached = self._should_keep_topk_only or (self.dense_probs is False and not self.compute_pbar)
+            if not (self.hpd_is_frozen() and cached):
+                return None
+            frozen = ops.BLEND_CODES[should_softmax_topk_features]
+        dev = self.encoding._hash_tables[0].weight.device
+        if not dev.type == "cuda":
+            return None
+        fresh = self._row_map is None or self._row_map.device != dev
+        if fresh:
+            from ._lib import query
+            L, T = self._num_levels, self._hash_table_size
+            assert query("gngf_slot_bitmap_words", L, 1, T) == L * ((T + 31) // 32)
+            self._row_map = torch.zeros((L, (T + 31) // 32), dtype=torch.int32, device=dev)
+            if self._hash_mode:
+                vs = self._n_max + 2
+                self._mark_reachable_rows(None, vs, vs * vs)
+        if frozen is not None:
+            _tv, ti, _w, vstride, NV, _order = self._frozen_vertex_table(frozen)      # (marks when it has to rebuild)
+            if fresh:
+                self._mark_reachable_rows(ti, vstride, NV)
+        return self._row_map
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor, batch_percentage: float = 1.0, should_calc_counts: bool = False):

@@ -89,9 +89,134 @@ class FusedAdam(torch.optim.Optimizer):
         self._spares = []            # pinned buffers set aside for captures (no pinned allocation while capturing)
         self._table_key = None
         self._total_blocks = 0
+        self._mask_source = None     # set_mask_source(): callable -> {parameter: (row map words, row_elems)} | None
+        # What the moments are known to fit: True — any map (there are no moments yet); None — unknown (loaded state, a source
+        # attached to existing state, dense steps taken); else the (maps, groups without weight decay) of the last masked
+        # step.  A step that resolves anything else checks the moments first (_guard).
+        self._fits = True
+        self._masked = False         # the segment table in self._table is followed by mask records
+        self._last_call = None       # the library call the last step() made (tests)
 
     _RECORD = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("w", "<u8"), ("n", "<i8"), ("first", "<i8"),
                         ("group", "<i4"), ("flags", "<i4")])          # csrc/optim.hip: AdamSegment (64 bytes)
+    _MASK_RECORD = np.dtype([("mask", "<u8"), ("row_elems", "<i4"), ("reserved", "<i4")])      # csrc/optim.hip: AdamSegMask (16 bytes)
+
+    @staticmethod
+    def mask_record(mask_ptr, row_elems, lo):
+        """(pointer, row_elems) of one segment's mask record.  A segment that starts at element `lo` of its parameter
+        (_adam_range) starts at row lo / row_elems of the map: the pointer is advanced by whole 32-bit words, which needs
+        lo % (32 * row_elems) == 0 — otherwise (0, 0): the record of a dense segment."""
+        mask_ptr, row_elems, lo = int(mask_ptr), int(row_elems), int(lo)
+        if mask_ptr == 0 or row_elems <= 0 or lo < 0 or lo % (32 * row_elems) != 0:
+            return 0, 0
+        return mask_ptr + (lo // row_elems // 32) * 4, row_elems
+
+    @classmethod
+    def pack_records(cls, segs, masks, block_elems):
+        """Pure numpy: the bytes of the device table and its number of blocks.  segs: per segment (param, grad, exp_avg,
+        exp_avg_sq, master, n, group, flags, ...) with pointers as integers; masks: None (the table gngf_adam_step reads) or
+        per segment None | (mask pointer, row_elems, lo) — then the nseg 64-byte segment records are followed by nseg
+        16-byte mask records (gngf_adam_step_masked's seg_masks = table + 64 * nseg)."""
+        rec = np.zeros(len(segs), dtype=cls._RECORD)
+        total_blocks = 0
+        for i, sg in enumerate(segs):
+            pp, gp, mp, vp, wp, n, gi, flags = sg[:8]
+            rec[i] = (pp, gp, mp, vp, wp, n, total_blocks, gi, flags)
+            total_blocks += -(-n // block_elems)
+        raw = rec.view(np.uint8).reshape(-1)
+        if masks is not None:
+            if len(masks) != len(segs):
+                raise ValueError("one mask entry (or None) per segment")
+            mrec = np.zeros(len(segs), dtype=cls._MASK_RECORD)
+            for i, m in enumerate(masks):
+                if m is not None:
+                    mrec[i] = (*cls.mask_record(*m), 0)
+            raw = np.concatenate([raw, mrec.view(np.uint8).reshape(-1)])
+        return raw, total_blocks
+
+    def set_mask_source(self, source):
+        """source: a callable returning {parameter: (int32 device tensor of row-map words, row_elems)} or None, asked at
+        every step (get_optimizer(..., skip_unreachable_rows=True) binds net.reachable_rows).  While it gives a map, step()
+        runs gngf_adam_step_masked: rows whose bit is clear are neither read nor written.  That equals the dense step bit for
+        bit as long as such rows have zero moments — true for rows that never receive a gradient and an optimizer that
+        starts from nothing.  Moments that were not produced under the same map — state that exists already (here, or after
+        load_state_dict), steps that ran densely because the source gave None (a trainable HPD frozen later), a group whose
+        weight decay was non-zero before — are checked once at the next eager step that has a map, and the source is
+        dropped with a warning if they do not qualify.  None detaches."""
+        self._mask_source = source
+        if any("exp_avg" in st for st in self.state.values()):
+            self._fits = None
+        self._table_key = None
+
+    def _resolve_masks(self, segs):
+        """per segment None | (row-map words, row_elems, lo) from the mask source, or None: the dense step"""
+        if self._mask_source is None:
+            return None
+        given = self._mask_source()
+        if not given:
+            return None
+        out = []
+        for sg in segs:
+            p, lo = sg[9]
+            m = given.get(p)
+            if m is None:
+                out.append(None)
+                continue
+            words, row_elems = m[0], int(m[1])
+            if (words.dtype != torch.int32 or not words.is_cuda or not words.is_contiguous() or row_elems <= 0
+                    or words.numel() * 32 * row_elems < p.numel()):
+                raise ValueError("mask source: int32 contiguous device words, one bit per row of row_elems elements, covering the parameter")
+            out.append((words, row_elems, lo) if self.mask_record(words.data_ptr(), row_elems, lo)[0] else None)
+        return out if any(m is not None for m in out) else None
+
+    @torch.no_grad()
+    def _state_fits_masks(self, segs, masks):
+        """One device reduction, one synchronise: exp_avg and exp_avg_sq are zero on every masked-out row of every masked segment."""
+        bad = None
+        for sg, m in zip(segs, masks):
+            if m is None:
+                continue
+            (p, lo), n = sg[9], sg[5]
+            words, re_, _lo = m
+            if float(self.param_groups[sg[6]]["weight_decay"]) != 0.0:
+                continue                                   # the kernel takes this segment densely
+            st = self.state[p]
+            nz = (st["exp_avg"].reshape(-1)[lo:lo + n] != 0) | (st["exp_avg_sq"].reshape(-1)[lo:lo + n] != 0)
+            rows = -(-n // re_)
+            if rows * re_ != n:
+                nz = torch.cat([nz, nz.new_zeros(rows * re_ - n)])
+            w0 = lo // re_ // 32
+            w = words.reshape(-1)[w0:w0 + -(-rows // 32)]
+            bits = ((w[:, None] >> torch.arange(32, device=w.device, dtype=torch.int32)) & 1).bool().reshape(-1)[:rows]
+            b = (nz.reshape(rows, re_).any(1) & ~bits).any()
+            bad = b if bad is None else bad | b
+        return bad is None or not bool(bad.item())
+
+    def _fit_key(self, masks):
+        """what a masked step relies on: these maps, and these groups taken row by row (the others are dense in the kernel)"""
+        return (tuple(None if m is None else (m[0].data_ptr(), m[1]) for m in masks),
+                tuple(float(g["weight_decay"]) == 0.0 for g in self.param_groups))
+
+    def _guard(self, segs, masks, capturing=False):
+        """masks when the moments are known to fit them, else None: the dense step.  Moments of unknown origin are checked
+        once, with one synchronise — never inside a capture (that step stays dense and the check waits for an eager step);
+        when they do not fit, the source is dropped: dense from now on."""
+        if masks is None:
+            return None
+        key = self._fit_key(masks)
+        if self._fits is True or self._fits == key:
+            self._fits = key
+            return masks
+        if capturing:
+            return None
+        if self._state_fits_masks(segs, masks):
+            self._fits = key
+            return masks
+        import warnings
+        warnings.warn("FusedAdam: the optimizer state has non-zero moments on rows outside the reachable-row map; "
+                      "skipping those rows would change results — the mask source is dropped, steps stay dense")
+        self._mask_source = None
+        return None
 
     def _segments(self):
         """fp32 parameters: torch.optim.Adam's state layout.  fp16 parameters (fp16 level tables, BASELINE config 5): fp32
@@ -131,7 +256,7 @@ class FusedAdam(torch.optim.Optimizer):
                     continue
                 segs.append((p.data_ptr() + lo * p.element_size(), g.data_ptr() + lo * g.element_size(), st["exp_avg"].data_ptr() + lo * 4,
                              st["exp_avg_sq"].data_ptr() + lo * 4, (st["master"].data_ptr() + lo * 4) if half else 0, hi - lo, gi,
-                             int(half) | (2 if g32 is not None else 0), g))
+                             int(half) | (2 if g32 is not None else 0), g, (p, lo)))
         return segs
 
     def zero_grad(self, set_to_none=True):
@@ -145,7 +270,9 @@ class FusedAdam(torch.optim.Optimizer):
         """Sets aside the pinned staging buffers a hipGraph capture of `steps` step() calls needs (pinned memory cannot be
         allocated while a stream captures) WITHOUT taking a step: call after one backward pass, before capturing."""
         segs = self._segments()
-        size = len(segs) * self._RECORD.itemsize
+        capturing = torch.cuda.is_current_stream_capturing()
+        masks = self._guard(segs, self._resolve_masks(segs), capturing)
+        size = len(segs) * (self._RECORD.itemsize + (self._MASK_RECORD.itemsize if masks is not None else 0))
         have = [h for h in self._spares if h.numel() == size]
         for _ in range(max(0, 1 + int(steps) - len(have))):
             self._spares.append(torch.empty((size,), dtype=torch.uint8, pin_memory=True))
@@ -161,17 +288,18 @@ class FusedAdam(torch.optim.Optimizer):
         segs = self._segments()
         if not segs:
             return loss
-        key = tuple(s_[:8] for s_ in segs)
         capturing = torch.cuda.is_current_stream_capturing()
-        table, total_blocks = self._table, self._total_blocks
+        masks = self._guard(segs, self._resolve_masks(segs), capturing)
+        if masks is None:
+            self._fits = None        # a dense step: the moments it leaves are not known to fit a map that appears later
+        mkey = None if masks is None else tuple(None if m is None else (m[0].data_ptr(), m[1]) for m in masks)
+        key = (tuple(s_[:8] for s_ in segs), mkey)
+        table, total_blocks, masked = self._table, self._total_blocks, self._masked
         if capturing or key != self._table_key:    # pointers moved (first step, new gradient buffers, loaded state)
-            blk = query("gngf_adam_block_elems")
-            rec = np.zeros(len(segs), dtype=self._RECORD)
-            total_blocks = 0
-            for i, (pp, gp, mp, vp, wp, n, gi, flags, _keep) in enumerate(segs):
-                rec[i] = (pp, gp, mp, vp, wp, n, total_blocks, gi, flags)
-                total_blocks += -(-n // blk)
-            raw = rec.view(np.uint8).reshape(-1)
+            masked = masks is not None
+            raw, total_blocks = self.pack_records(
+                segs, None if masks is None else [None if m is None else (m[0].data_ptr(), m[1], m[2]) for m in masks],
+                query("gngf_adam_block_elems"))
             dev = self._step.device
             # Pinned staging + asynchronous copy.  Inside a hipGraph capture (gradients allocated from the graph's pool have
             # their own addresses) the copy becomes a node of the graph, so the captured step owns a private staging buffer
@@ -203,13 +331,19 @@ class FusedAdam(torch.optim.Optimizer):
                 self._table.copy_(slot[0], non_blocking=True)
                 slot[1] = torch.cuda.Event()
                 slot[1].record()
-                self._table_key, self._total_blocks, table = key, total_blocks, self._table
+                self._table_key, self._total_blocks, self._masked, table = key, total_blocks, masked, self._table
         ng = len(self.param_groups)
         lr = (ctypes.c_float * ng)(*[float(g["lr"]) for g in self.param_groups])
         wd = (ctypes.c_float * ng)(*[float(g["weight_decay"]) for g in self.param_groups])
         b1, b2 = self.param_groups[0]["betas"]
-        call("gngf_adam_step", ptr(table), len(segs), total_blocks, ptr(self._step), lr, wd, ng, float(b1), float(b2),
-             float(self.param_groups[0]["eps"]), 1.0 / float(self.grad_scale), stream_ptr())
+        args = (ptr(table), len(segs), total_blocks, ptr(self._step), lr, wd, ng, float(b1), float(b2),
+                float(self.param_groups[0]["eps"]), 1.0 / float(self.grad_scale))
+        self._last_call = "gngf_adam_step_masked" if masked else "gngf_adam_step"
+        if masked:
+            # (the mask records follow the segment records in the same table: same staging, same ring, same capture rules)
+            call("gngf_adam_step_masked", *args, ctypes.c_void_p(table.data_ptr() + len(segs) * self._RECORD.itemsize), stream_ptr())
+        else:
+            call("gngf_adam_step", *args, stream_ptr())
         return loss
 
     def state_dict(self):
@@ -234,13 +368,27 @@ class FusedAdam(torch.optim.Optimizer):
                     self.state[p][k] = src[k].detach().to(device=p.device, dtype=torch.float32).clone()
         self._step = None                          # re-read from the loaded per-parameter `step`
         self._table_key = None
+        self._fits = None                          # loaded moments: checked against the map at the next eager step that has one
+
+
+def level_mask_source(net):
+    """The mask source of FusedAdam.set_mask_source for a model's level tables: level l's parameter (net.dp.level_params[l], a
+    (T, F) table: one row = F elements) is paired with row l of net.reachable_rows(); None while the model has no such map."""
+    def source():
+        rows = net.reachable_rows()
+        if rows is None:
+            return None
+        return {p: (rows[l], int(p.shape[-1])) for l, p in enumerate(net.dp.level_params)}
+    return source
 
 
 def get_optimizer(net, encoding_lr, HPD_lr, MLP_lr, encoding_weight_decay, HPD_weight_decay, MLP_weight_decay,
-                  betas=(0.9, 0.99), eps=1e-15, fused_kernel=None):
+                  betas=(0.9, 0.99), eps=1e-15, fused_kernel=None, *, skip_unreachable_rows=False):
     """reference functions.py:96-127.  On the GPU the update runs as one launch of this package's Adam kernel
     (FusedAdam: same rule and state layout as torch.optim.Adam); host tensors (CPU tests of the training algebra) and
-    fused_kernel=False use torch.optim.Adam itself."""
+    fused_kernel=False use torch.optim.Adam itself.
+    skip_unreachable_rows (keyword-only, extension; FusedAdam only): the step visits only the level-table rows the model can
+    address (net.reachable_rows(): coordinates in [0, 1]^2) — the same result bit for bit, see FusedAdam.set_mask_source."""
     groups = [{"params": list(net.encoding.parameters()), "lr": encoding_lr, "weight_decay": encoding_weight_decay}]
     if not models.should_use_hash_function:
         groups.append({"params": list(net.HPD.parameters()), "lr": HPD_lr, "weight_decay": HPD_weight_decay})
@@ -252,7 +400,10 @@ def get_optimizer(net, encoding_lr, HPD_lr, MLP_lr, encoding_weight_decay, HPD_w
     if fused_kernel is None:
         fused_kernel = on_gpu
     if fused_kernel:
-        return FusedAdam(groups, betas=betas, eps=eps)
+        opt = FusedAdam(groups, betas=betas, eps=eps)
+        if skip_unreachable_rows:
+            opt.set_mask_source(level_mask_source(net))
+        return opt
     enc = getattr(net, "encoding", None)
     handover = getattr(enc, "grad_fp32_handover", None)
     handover = ops.FP16_TABLE_GRAD_FP32 if handover is None else handover

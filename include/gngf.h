@@ -430,6 +430,14 @@ int gngf_distinct_slot_counts(const int64_t* indices, int64_t P, int L, int V, i
 int gngf_mark_batch_slots(const float* xy, const int32_t* n_ls, int64_t P, int L, const int32_t* vert_idx, int K, int64_t T,
                           int vstride, int64_t NV, uint32_t* touched, uint32_t* bitmap, void* stream);
 int gngf_count_slot_bits(const uint32_t* bitmap, int L, int K, int64_t T, int32_t* counts, void* stream);
+/* The rows a model can EVER address, whatever the batch (coordinates in [0,1]^2): for every level l and every vertex
+ * 0 <= gx, gy <= N_l + 1 (the corners of weight 0 at N_l + 1 included) ORs into `rowmask` — gngf_slot_bitmap_words(L, 1, T)
+ * words laid out (L, ceil(T / 32)), bit (slot & 31) of word (slot >> 5); never cleared by the call, the caller zero-fills it
+ * once — row spatial_hash(gx, gy) when vert_idx == NULL (K = 1), else the K rows vert_idx[(gy * vstride + gx) * K + k]
+ * (vertices with gx >= vstride or beyond NV are not in the table and are skipped).  n_ls: device, n_ls_host: the same L
+ * values on the host.  A superset of the rows that can receive a non-zero gradient: what gngf_adam_step_masked may skip. */
+int gngf_mark_reachable_rows(const int32_t* n_ls, const int32_t* n_ls_host, int L, const int32_t* vert_idx, int K, int64_t T,
+                             int vstride, int64_t NV, uint32_t* rowmask, void* stream);
 
 /* ---- optimizer (row f2: the caller of the path) ---------------------------------------------------------------------
  * torch.optim.Adam as get_optimizer builds it (functions.py:96-127: betas (0.9, 0.99), eps 1e-15, L2-style weight
@@ -450,6 +458,16 @@ int gngf_adam_block_elems(void);
 int gngf_adam_step(const void* segments, int nseg, int64_t total_blocks, float* step, const float* lr,
                    const float* weight_decay, int ngroups, float beta1, float beta2, float eps, float inv_grad_scale,
                    void* stream);
+/* The same step over reachable table rows only.  seg_masks: device array of nseg 16-byte records
+ *     { const uint32_t* mask; int32_t row_elems; int32_t reserved; }
+ * element e of segment i belongs to row e / row_elems and is processed when bit (row & 31) of mask[row >> 5] is set
+ * (gngf_mark_reachable_rows writes such maps); rows whose bit is clear are neither read nor written.  mask == NULL: the
+ * segment is processed densely — as is every segment of a group with weight_decay != 0 (decided by the kernel: with decay
+ * an unreachable row does change).  Equal to gngf_adam_step bit for bit provided the moments of every masked-out row are 0,
+ * which holds for rows that never receive a gradient. */
+int gngf_adam_step_masked(const void* segments, int nseg, int64_t total_blocks, float* step, const float* lr,
+                          const float* weight_decay, int ngroups, float beta1, float beta2, float eps, float inv_grad_scale,
+                          const void* seg_masks, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,631 @@
+"""GPU: the row-masked Adam step (csrc/optim.hip: gngf_adam_step_masked) and the reachable-row map it reads (csrc/stats.hip:
+gngf_mark_reachable_rows; models.GeneralNeuralGaugeFields.reachable_rows) — bit for bit against the dense step.
+
+The claim is bitwise, so every comparison is torch.equal.  Two INDEPENDENT training runs are not bitwise equal on this
+path even when both are dense (the table gradient is summed with float atomics whose order changes from run to run, see
+tests/test_gpu_bucket.py), so the training tests hand both optimizers the SAME gradient tensors: model A runs forward and
+backward, its dense optimizer steps, and model B — an identical copy with get_optimizer(..., skip_unreachable_rows=True) —
+steps on A's gradients inside the same optimizer.step() (eager, and captured in the same hipGraph).  If the masked step is
+exact, A and B stay identical for ever, so A's gradients are B's."""
+import copy
+import ctypes
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import gngf_oracle as orc
+from test_adam_mask_cpu import expected_hash_row_map, expected_table_row_map, popcount, set_bits
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+
+def bits_equal(a, b):
+    """bitwise equality (NaN payloads and signed zeros included)"""
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return False
+    it = {torch.float32: torch.int32, torch.float16: torch.int16}.get(a.dtype, a.dtype)
+    return torch.equal(a.contiguous().view(it), b.contiguous().view(it))
+
+
+def as_u32(t):
+    return t.detach().cpu().numpy().view(np.uint32)
+
+
+# ------------------------------------------------------------------------------------------------ 1. the map
+def mark(n_ls, T, rowmask, vert_idx=None, vstride=0, NV=0):
+    from collision_handling_in_instantngp_amd._lib import call, ptr, stream_ptr
+    L = len(n_ls)
+    host = (ctypes.c_int32 * L)(*[int(n) for n in n_ls])
+    dev_n = torch.tensor([int(n) for n in n_ls], dtype=torch.int32, device=DEV)
+    K = 1 if vert_idx is None else vert_idx.shape[1]
+    call("gngf_mark_reachable_rows", ptr(dev_n), host, L, ptr(vert_idx, torch.int32), K, T, int(vstride), int(NV), ptr(rowmask), stream_ptr())
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("L,n_min,n_max,T", [(4, 4, 32, 1000), (8, 8, 256, 2 ** 14), (8, 8, 256, 2 ** 16)])
+def test_reachable_row_map_hash_mode_equals_numpy(L, n_min, n_max, T):
+    """T = 1000: no power of two (the % form of the hash), a partial last word, fine levels saturate; T = 2^14 / 2^16:
+    sparse coarse levels.  A second call adds nothing; bits that were there stay."""
+    from collision_handling_in_instantngp_amd._lib import query
+    n_ls = orc.level_resolutions(n_min, n_max, L)
+    words = (T + 31) // 32
+    assert query("gngf_slot_bitmap_words", L, 1, T) == L * words
+    want = expected_hash_row_map(n_ls, T)
+    m = torch.zeros((L, words), dtype=torch.int32, device=DEV)
+    mark(n_ls, T, m)
+    assert np.array_equal(as_u32(m), want)
+    for l, n in enumerate(n_ls):
+        assert 0 < popcount(want[l]) <= min(T, (int(n) + 2) ** 2)
+    mark(n_ls, T, m)
+    assert np.array_equal(as_u32(m), want)
+    pre = torch.zeros_like(m)
+    pre[:, 0] = 0x5
+    pre[-1, -1] = 1                                            # (bit 0 of the last word: a row below T at all three shapes)
+    keep = as_u32(pre).copy()
+    mark(n_ls, T, pre)
+    assert np.array_equal(as_u32(pre), want | keep)            # OR-accumulated, never cleared
+
+
+def frozen_net(models, T=2048, L=4, F=2, K=4, n_min=4, n_max=32, seed=7, table_dtype=torch.float32):
+    torch.manual_seed(seed)
+    net = models.GeneralNeuralGaugeFields(input_dim=2, hash_table_size=T, num_levels=L, n_min=n_min, n_max=n_max,
+                                          MLP_hidden_layers_widths=[64, 64], HPD_hidden_layers_widths=[32, 64, 128],
+                                          HPD_out_features=T, feature_dim=F, topk_k=K, table_dtype=table_dtype)
+    for p in net.HPD.parameters():
+        p.requires_grad = False
+    net.dense_probs = False
+    net.compute_pbar = False
+    net.return_indices = False
+    return net
+
+
+def test_reachable_row_map_frozen_hpd_equals_union_over_k_of_the_cached_table():
+    from collision_handling_in_instantngp_amd import models
+    assert not models.should_use_hash_function
+    T, L, K = 2048, 4, 4
+    net = frozen_net(models, T=T, L=L, K=K)
+    m = net.reachable_rows()
+    torch.cuda.synchronize()
+    assert m is not None and m.dtype == torch.int32 and tuple(m.shape) == (L, T // 32)
+    _tv, ti, _w, vstride, NV, _order = net._frozen_table[1:]
+    assert tuple(ti.shape) == (NV, K) and vstride == 34
+    want = expected_table_row_map(net._n_ls_host, T, ti.cpu().numpy(), vstride)
+    assert np.array_equal(as_u32(m), want)
+    assert all(0 < popcount(want[l]) <= min(T, K * (n + 2) ** 2) for l, n in enumerate(net._n_ls_host))
+    assert popcount(want[0]) < T // 4                          # the coarse level (36 vertices x 4) leaves most rows out
+    # the same tensor every time; a rebuilt table (the HPD's weights changed) ORs its rows in
+    addr = m.data_ptr()
+    assert net.reachable_rows().data_ptr() == addr
+    with torch.no_grad():
+        for p in net.HPD.parameters():
+            p.add_(torch.randn_like(p) * 0.5)
+    m2 = net.reachable_rows()
+    torch.cuda.synchronize()
+    assert m2.data_ptr() == addr
+    ti2 = net._frozen_table[2]
+    want2 = expected_table_row_map(net._n_ls_host, T, ti2.cpu().numpy(), vstride)
+    assert not np.array_equal(want, want2)
+    assert np.array_equal(as_u32(m2), want | want2)
+    # the entry point on a second, arbitrary table (vstride narrower than the finest level: those vertices are skipped)
+    g = torch.Generator().manual_seed(1)
+    vs3, K3 = 20, 3
+    t3 = torch.randint(0, T, (vs3 * vs3 - 5, K3), generator=g, dtype=torch.int32)
+    t3[::7, 1] = -1                                            # not a row: ignored
+    t3[3::11, 2] = T
+    mm = torch.zeros((L, T // 32), dtype=torch.int32, device=DEV)
+    mark(net._n_ls_host, T, mm, t3.to(DEV), vs3, t3.shape[0])
+    assert np.array_equal(as_u32(mm), expected_table_row_map(net._n_ls_host, T, t3.numpy(), vs3))
+
+
+# ------------------------------------------------------------------------------------------------ direct calls of the two kernels
+LR, B1, B2, EPS = 1e-2, 0.9, 0.99, 1e-15
+
+
+def adam_call(p, g, m, v, master, flags, mask=None, row_elems=0, wd=0.0, steps_before=0.0, force_masked=False):
+    """one step of gngf_adam_step (mask None) or gngf_adam_step_masked over ONE segment, in place"""
+    from collision_handling_in_instantngp_amd._lib import call, ptr, query, stream_ptr
+    from collision_handling_in_instantngp_amd.train import FusedAdam
+    seg = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), 0 if master is None else master.data_ptr(), p.numel(), 0, flags)
+    masked = mask is not None or force_masked
+    masks = None if not masked else [None if mask is None else (mask.data_ptr(), row_elems, 0)]
+    raw, blocks = FusedAdam.pack_records([seg], masks, query("gngf_adam_block_elems"))
+    table = torch.from_numpy(raw.copy()).to(DEV)
+    step = torch.full((), float(steps_before), dtype=torch.float32, device=DEV)
+    lr, wdv = (ctypes.c_float * 1)(LR), (ctypes.c_float * 1)(wd)
+    args = (ptr(table), 1, blocks, ptr(step), lr, wdv, 1, B1, B2, EPS, 1.0)
+    if masked:
+        call("gngf_adam_step_masked", *args, ctypes.c_void_p(table.data_ptr() + 64), stream_ptr())
+    else:
+        call("gngf_adam_step", *args, stream_ptr())
+    torch.cuda.synchronize()
+    assert float(step) == steps_before + 1.0
+
+
+FLAVOURS = {"fp32": 0, "fp16": 1, "fp16_grad32": 3}
+
+
+def make_state(T, F, flavour, off, seed):
+    """p, g, m, v, master as (T, F) views that start `off` elements into their allocations (off = 1: not 16-byte aligned)"""
+    gen = torch.Generator().manual_seed(seed)
+    flags = FLAVOURS[flavour]
+    n = T * F
+
+    def buf(dtype, scale, positive=False):
+        x = torch.randn(n + off, generator=gen) * scale
+        x = x.abs() if positive else x
+        return x.to(dtype).to(DEV)
+    pd = torch.float16 if flags & 1 else torch.float32
+    gd = torch.float16 if flags == 1 else torch.float32
+    master = buf(torch.float32, 0.1) if flags & 1 else None
+    p = master.to(pd).clone() if flags & 1 else buf(pd, 0.1)
+    st = {"p": p, "g": buf(gd, 1e-2), "m": buf(torch.float32, 1e-3), "v": buf(torch.float32, 1e-5, positive=True), "master": master}
+    return {k: (None if x is None else x[off:].view(T, F)) for k, x in st.items()}, flags
+
+
+def clone_state(st):
+    # (clones of the offset views keep their misalignment only if cloned through an offset buffer)
+    out = {}
+    for k, x in st.items():
+        if x is None:
+            out[k] = None
+            continue
+        off = x.storage_offset()
+        b = torch.empty(x.numel() + off, dtype=x.dtype, device=x.device)
+        out[k] = b[off:].view(x.shape)
+        out[k].copy_(x)
+        assert out[k].data_ptr() % 16 == x.data_ptr() % 16
+    return out
+
+
+def mask_words(rows_bool):
+    T = rows_bool.shape[0]
+    w = np.zeros(((T + 31) // 32,), dtype=np.uint32)
+    set_bits(w, np.flatnonzero(rows_bool))
+    return torch.from_numpy(w.view(np.int32)).to(DEV)
+
+
+@pytest.mark.parametrize("flavour", list(FLAVOURS))
+@pytest.mark.parametrize("F", [1, 2, 4, 8])
+def test_masked_step_never_touches_masked_out_rows_and_equals_dense_on_the_others(F, flavour):
+    """NaN in every masked-out row of gradient, parameter, moments (and master): those rows are bit-identical afterwards — they
+    were neither read into a result nor written — and the masked-in rows equal the dense kernel's result on a copy that holds
+    zeros where the NaNs were.  T = 3001 rows: several blocks of 2048 elements, a partial last block, a scalar tail at F = 1, 2, a
+    partial last mask word.  Masks: none set (every block leaves at once), all set, one row per block, random (float4s with
+    reachable and unreachable rows side by side at F < 4).  Also on tensors that start one element into their allocation."""
+    T = 3001
+    rng = np.random.default_rng(100 + F)
+    rows_per_block = max(1, 2048 // F)
+    one_per_block = np.zeros(T, bool)
+    for b, r0 in enumerate(range(0, T, rows_per_block)):
+        one_per_block[min(T - 1, r0 + (37 * b + 5) % rows_per_block)] = True
+    shapes = {"none": np.zeros(T, bool), "all": np.ones(T, bool), "one_per_block": one_per_block, "random": rng.random(T) < 0.3}
+    for off in (0, 1):
+        for name, rows in shapes.items():
+            st, flags = make_state(T, F, flavour, off, seed=F * 10 + off)
+            assert (st["m"].data_ptr() % 16 == 0) == (off == 0)
+            keep = torch.from_numpy(rows).to(DEV)
+            dense = clone_state(st)
+            for x in st.values():
+                if x is not None:
+                    x[~keep] = float("nan")
+            for x in dense.values():
+                if x is not None:
+                    x[~keep] = 0
+            before = clone_state(st)
+            mw = mask_words(rows)
+            adam_call(st["p"], st["g"], st["m"], st["v"], st["master"], flags, mask=mw, row_elems=F, steps_before=3.0)
+            adam_call(dense["p"], dense["g"], dense["m"], dense["v"], dense["master"], flags, steps_before=3.0)
+            for k in ("p", "m", "v", "master"):
+                if st[k] is None:
+                    continue
+                what = (F, flavour, off, name, k)
+                assert bits_equal(st[k][~keep], before[k][~keep]), what              # untouched
+                assert bits_equal(st[k][keep], dense[k][keep]), what                 # = the dense step
+                if rows.any():
+                    assert not bits_equal(st[k][keep], before[k][keep]), what        # (and it did step)
+            assert bits_equal(st["g"], before["g"])
+
+
+@pytest.mark.parametrize("flavour", list(FLAVOURS))
+@pytest.mark.parametrize("F", [1, 2, 4, 8])
+def test_masked_out_rows_with_finite_state_and_gradient_stay_bit_identical(F, flavour):
+    """The NaN case above cannot tell a kernel that skips a row from one that reads and rewrites it (a NaN row comes back as
+    the same NaN).  Here the masked-out rows hold finite, distinct, non-zero parameter, moments, master and gradient: a
+    processed row changes (the dense step on a copy shows it does), a skipped row is bit-identical.  The masked-in rows equal
+    the dense step on that same copy (elements are independent)."""
+    T = 3001
+    rng = np.random.default_rng(200 + F)
+    rows_per_block = max(1, 2048 // F)
+    one_per_block = np.zeros(T, bool)
+    for b, r0 in enumerate(range(0, T, rows_per_block)):
+        one_per_block[min(T - 1, r0 + (53 * b + 11) % rows_per_block)] = True
+    shapes = {"none": np.zeros(T, bool), "one_per_block": one_per_block, "random": rng.random(T) < 0.3}
+    for off in (0, 1):
+        for name, rows in shapes.items():
+            st, flags = make_state(T, F, flavour, off, seed=F * 10 + off + 500)
+            keep = torch.from_numpy(rows).to(DEV)
+            for k in ("m", "v"):
+                assert bool((st[k] != 0).all()) and bool(torch.isfinite(st[k]).all())
+            assert bool(torch.isfinite(st["g"].float()).all()) and float((st["g"] != 0).float().mean()) > 0.99
+            before, dense = clone_state(st), clone_state(st)
+            adam_call(st["p"], st["g"], st["m"], st["v"], st["master"], flags, mask=mask_words(rows), row_elems=F, steps_before=3.0)
+            adam_call(dense["p"], dense["g"], dense["m"], dense["v"], dense["master"], flags, steps_before=3.0)
+            for k in ("p", "m", "v", "master"):
+                if st[k] is None:
+                    continue
+                what = (F, flavour, off, name, k)
+                assert bits_equal(st[k][~keep], before[k][~keep]), what              # skipped
+                assert bits_equal(st[k][keep], dense[k][keep]), what                 # = the dense step
+            # (processing a masked-out row would have changed it: the dense step moves the moments of every row)
+            changed = ((dense["m"] != before["m"]) | (dense["v"] != before["v"])).reshape(T, F).any(1)
+            assert bool(changed.all()), (F, flavour, off, name)
+            assert bits_equal(st["g"], before["g"])
+
+
+def test_weight_decay_makes_a_masked_segment_dense():
+    """With weight decay an unreachable row does change, so the kernel takes the segment densely although a map is attached
+    (decided on the device from the weight_decay array) — and that differs from leaving the masked-out rows alone."""
+    T, F = 3001, 2
+    rows = np.zeros(T, bool)
+    rows[::97] = True
+    keep = torch.from_numpy(rows).to(DEV)
+    st, flags = make_state(T, F, "fp32", 0, seed=5)
+    for k in ("g", "m", "v"):
+        st[k][~keep] = 0                                        # the state unreachable rows really have
+    before = clone_state(st)
+    dense, forced = clone_state(st), clone_state(st)
+    adam_call(st["p"], st["g"], st["m"], st["v"], None, flags, mask=mask_words(rows), row_elems=F, wd=1e-6)
+    adam_call(dense["p"], dense["g"], dense["m"], dense["v"], None, flags, wd=1e-6)
+    for k in ("p", "m", "v"):
+        assert bits_equal(st[k], dense[k]), k
+    # the mask forced: masked-out rows keep their values — not what weight decay does to them
+    for k in ("p", "m", "v"):
+        forced[k][keep] = dense[k][keep]
+        assert not bits_equal(forced[k], dense[k]), k
+    assert not bits_equal(st["p"][~keep], before["p"][~keep])
+    # without decay the same call does leave them alone
+    st0 = clone_state(before)
+    adam_call(st0["p"], st0["g"], st0["m"], st0["v"], None, flags, mask=mask_words(rows), row_elems=F, wd=0.0)
+    d0 = clone_state(before)
+    adam_call(d0["p"], d0["g"], d0["m"], d0["v"], None, flags, wd=0.0)
+    for k in ("p", "m", "v"):
+        assert bits_equal(st0[k], d0[k]), k                     # zero moments, zero gradient: the dense step is a no-op there
+        assert bits_equal(st0[k][~keep], before[k][~keep]), k
+    # a NULL map inside the masked entry point: dense
+    sn = clone_state(before)
+    adam_call(sn["p"], sn["g"], sn["m"], sn["v"], None, flags, mask=None, force_masked=True)
+    for k in ("p", "m", "v"):
+        assert bits_equal(sn[k], d0[k]), k
+
+
+# ------------------------------------------------------------------------------------------------ 2. training: masked == dense
+def twin(opt, opt_b, net, net_b):
+    """opt.step() also steps opt_b on the SAME gradient tensors (see the module docstring); prepare_capture likewise."""
+    pairs = list(zip(net.parameters(), net_b.parameters()))
+    step0, prep0 = opt.step, opt.prepare_capture
+
+    def hand_over():
+        for p, q in pairs:
+            q.grad = p.grad
+            g32 = getattr(p, "grad_fp32", None)
+            if g32 is not None or getattr(q, "grad_fp32", None) is not None:
+                q.grad_fp32 = g32
+
+    def step(closure=None):
+        r = step0()
+        hand_over()
+        opt_b.step()
+        return r
+
+    def prepare_capture(steps=1):
+        prep0(steps)
+        hand_over()
+        opt_b.prepare_capture(steps)
+    opt.step, opt.prepare_capture = step, prepare_capture
+
+
+def assert_same_state(net, net_b, opt, opt_b, what):
+    n = 0
+    for (k, p), (_k, q) in zip(net.named_parameters(), net_b.named_parameters()):
+        assert bits_equal(p.detach(), q.detach()), (what, k)
+        sa, sb = opt.state.get(p, {}), opt_b.state.get(q, {})
+        assert set(sa) == set(sb), (what, k)
+        for name in ("exp_avg", "exp_avg_sq", "master"):
+            if name in sa:
+                assert bits_equal(sa[name], sb[name]), (what, k, name)
+                n += 1
+        if "step" in sa:
+            assert float(sa["step"]) == float(sb["step"])
+    return n
+
+
+def batches_xy(n, seed):
+    g = torch.Generator().manual_seed(seed)
+    X = torch.rand((n, 2), generator=g)
+    X[:4] = torch.tensor([[0.0, 0.0], [1.0, 1.0], [0.0, 1.0], [1.0, 0.0]])          # the corners at N_l and N_l + 1
+    X[4:8, 0] = 1.0
+    return X.to(DEV).contiguous(), torch.rand((n, 3), generator=g).to(DEV)
+
+
+CASES = {
+    # name: (mode, L, n_min, n_max, T, F, table dtype, fp32 gradient hand-over)
+    "hash_T1000_F2": ("hash", 4, 4, 32, 1000, 2, torch.float32, None),
+    "hash_T1000_F2_fp16": ("hash", 4, 4, 32, 1000, 2, torch.float16, False),
+    "hash_T1000_F4_fp16_grad32": ("hash", 4, 4, 32, 1000, 4, torch.float16, True),
+    "hash_T16k_F1": ("hash", 8, 8, 256, 2 ** 14, 1, torch.float32, None),
+    "hash_T16k_F2": ("hash", 8, 8, 256, 2 ** 14, 2, torch.float32, None),
+    "hash_T16k_F8": ("hash", 8, 8, 256, 2 ** 14, 8, torch.float32, None),
+    "gngf_frozen_K4_T2048_F2": ("gngf", 4, 4, 32, 2048, 2, torch.float32, None),
+}
+
+
+@pytest.mark.parametrize("graph", [False, True])
+@pytest.mark.parametrize("case", list(CASES))
+def test_five_training_steps_masked_equal_dense_bit_for_bit(case, graph):
+    """get_optimizer(...) against get_optimizer(..., skip_unreachable_rows=True) over five steps on five seeded random batches
+    (train.train_epoch; graph=True: every step replayed from a hipGraph with both optimizer steps inside): every parameter,
+    exp_avg, exp_avg_sq and fp32 master torch.equal — no tolerance.  The T = 1000 (L = 4, N 4 -> 32: no segment a multiple of
+    2048 elements) and T = 2^14 (L = 8, N 8 -> 256) shapes, F = 1, 2, 4, 8 between them; fp32 tables, fp16 tables with fp16 and
+    with fp32 gradients; a frozen HPD at K = 4."""
+    from collision_handling_in_instantngp_amd import models, ops, train
+    mode, L, n_min, n_max, T, F, dtype, g32 = CASES[case]
+    models.should_use_hash_function = mode == "hash"
+    prev_g32 = ops.FP16_TABLE_GRAD_FP32
+    if g32 is not None:
+        ops.FP16_TABLE_GRAD_FP32 = g32
+    try:
+        if mode == "hash":
+            torch.manual_seed(11)
+            net = models.GeneralNeuralGaugeFields(input_dim=2, hash_table_size=T, num_levels=L, n_min=n_min, n_max=n_max,
+                                                  MLP_hidden_layers_widths=[64, 64], HPD_hidden_layers_widths=[32, 64, 128],
+                                                  HPD_out_features=T, feature_dim=F, topk_k=4, table_dtype=dtype)
+            net.return_indices = False
+        else:
+            net = frozen_net(models, T=T, L=L, F=F, K=4, n_min=n_min, n_max=n_max)
+        if dtype == torch.float16:
+            with torch.no_grad():
+                for m in net.encoding._hash_tables:
+                    m.weight.mul_(100.0)
+        net_b = copy.deepcopy(net)
+        start = {k: p.detach().clone() for k, p in net.named_parameters()}
+        opt = train.get_optimizer(net, 1e-2, 1e-3, 1e-3, 0.0, 0.0, 1e-6)
+        opt_b = train.get_optimizer(net_b, 1e-2, 1e-3, 1e-3, 0.0, 0.0, 1e-6, skip_unreachable_rows=True)
+        assert isinstance(opt, train.FusedAdam) and opt._mask_source is None and opt_b._mask_source is not None
+        twin(opt, opt_b, net, net_b)
+        side = 100
+        X, Y = batches_xy(side * side, seed=3)
+        loss_fn = train.Loss(delta=1, gamma=-2, epsilon=1)
+        train.train_epoch(net, loss_fn, opt, X, Y, side, side, 1, 1, 1e-3, batch_percentage=1 / 5, should_shuffle=False, graph=graph)
+        torch.cuda.synchronize()
+        assert (opt._last_call, opt_b._last_call) == ("gngf_adam_step", "gngf_adam_step_masked")
+        assert float(opt._step) == 5.0 and float(opt_b._step) == 5.0
+        compared = assert_same_state(net, net_b, opt, opt_b, case)
+        assert compared >= 2 * (L + 6) + (L if dtype == torch.float16 else 0)
+        moved = [not torch.equal(p.detach(), start[k]) for k, p in net.named_parameters() if "_hash_tables" in k]
+        # every level table was trained (fp16 gradients of single levels may underflow without a loss scale: one is enough there)
+        assert len(moved) == L and (all(moved) if (dtype == torch.float32 or g32) else any(moved)), moved
+        # the map is a strict subset of the coarse level's rows, and the moments outside it are still exactly zero
+        rows = net_b.reachable_rows()
+        w0 = net_b.encoding._hash_tables[0].weight
+        bits = torch.from_numpy(np.unpackbits(as_u32(rows[0]).view(np.uint8), bitorder="little")[:T].astype(bool)).to(DEV)
+        assert 0 < int(bits.sum()) < T
+        for name in ("exp_avg", "exp_avg_sq"):
+            assert float(opt.state[net.encoding._hash_tables[0].weight][name][~bits].abs().max()) == 0.0
+            assert float(opt_b.state[w0][name][~bits].abs().max()) == 0.0
+            assert float(opt_b.state[w0][name][bits].abs().max()) > 0.0
+    finally:
+        ops.FP16_TABLE_GRAD_FP32 = prev_g32
+        models.should_use_hash_function = False
+
+
+# ------------------------------------------------------------------------------------------------ 5. the state guard
+def hash_net(models, T=2 ** 14, L=8, F=2, seed=21):
+    torch.manual_seed(seed)
+    net = models.GeneralNeuralGaugeFields(input_dim=2, hash_table_size=T, num_levels=L, n_min=8, n_max=256,
+                                          MLP_hidden_layers_widths=[64, 64], HPD_hidden_layers_widths=[32, 64, 128],
+                                          HPD_out_features=T, feature_dim=F, topk_k=4)
+    net.return_indices = False
+    return net
+
+
+def one_step(net, opt, X, Y):
+    opt.zero_grad()
+    rgb, _p, _i, _c = net(X, 1.0)
+    torch.nn.functional.mse_loss(rgb, Y).backward()
+    opt.step()
+
+
+@pytest.mark.parametrize("clean", [False, True])
+def test_loaded_state_is_checked_once_against_the_map(clean):
+    """A loaded state with a non-zero moment on a masked-out row: the next step warns, drops the map and equals dense from then
+    on.  A clean loaded state keeps the masked step (and equals dense as well)."""
+    from collision_handling_in_instantngp_amd import models, train
+    models.should_use_hash_function = True
+    try:
+        net = hash_net(models)
+        X, Y = batches_xy(4000, seed=8)
+        opt0 = train.get_optimizer(net, 1e-2, 1e-3, 1e-3, 0.0, 0.0, 1e-6)
+        one_step(net, opt0, X[:2000], Y[:2000])
+        rows = net.reachable_rows()
+        bits0 = np.unpackbits(as_u32(rows[0]).view(np.uint8), bitorder="little").astype(bool)
+        out_row = int(np.flatnonzero(~bits0)[17])
+        sd = copy.deepcopy(opt0.state_dict())
+        if not clean:
+            sd["state"][0]["exp_avg_sq"][out_row, 1] = 1e-3     # parameter 0 = level 0's table
+        net_b = copy.deepcopy(net)
+        opt = train.get_optimizer(net, 1e-2, 1e-3, 1e-3, 0.0, 0.0, 1e-6)
+        opt_b = train.get_optimizer(net_b, 1e-2, 1e-3, 1e-3, 0.0, 0.0, 1e-6, skip_unreachable_rows=True)
+        opt.load_state_dict(copy.deepcopy(sd))
+        opt_b.load_state_dict(copy.deepcopy(sd))
+        assert opt_b._fits is None
+        twin(opt, opt_b, net, net_b)
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            one_step(net, opt, X[2000:], Y[2000:])
+        said = [w for w in caught if "reachable-row map" in str(w.message)]
+        assert (opt_b._fits is not None) == clean
+        if clean:
+            assert not said and opt_b._mask_source is not None and opt_b._last_call == "gngf_adam_step_masked"
+        else:
+            assert len(said) == 1 and opt_b._mask_source is None and opt_b._last_call == "gngf_adam_step"
+        one_step(net, opt, X[:2000], Y[:2000])
+        assert opt_b._last_call == ("gngf_adam_step_masked" if clean else "gngf_adam_step")
+        assert float(opt_b._step) == 3.0
+        assert assert_same_state(net, net_b, opt, opt_b, f"clean={clean}") > 0
+        # attaching a source to an optimizer that already has state arms the same check
+        opt.set_mask_source(train.level_mask_source(net))
+        assert opt._fits is None
+    finally:
+        models.should_use_hash_function = False
+
+
+def test_weight_decay_switched_off_after_steps_is_checked_before_the_map_is_used():
+    """A group that had weight decay was stepped densely (the kernel's rule), so its moments are non-zero outside the map.  Once
+    its weight decay is set to 0 the map would apply: the next step checks first, warns, and stays equal to the dense optimizer."""
+    from collision_handling_in_instantngp_amd import train
+    T, F = 3001, 2
+    gen = torch.Generator().manual_seed(31)
+    rows = np.zeros(T, bool)
+    rows[::97] = True
+    keep = torch.from_numpy(rows).to(DEV)
+    words = mask_words(rows)
+    p0 = (torch.randn((T, F), generator=gen) * 0.1).to(DEV)
+    pa, pb = torch.nn.Parameter(p0.clone()), torch.nn.Parameter(p0.clone())
+    opt_a = train.FusedAdam([pa], lr=LR, betas=(B1, B2), eps=EPS, weight_decay=1e-6)
+    opt_b = train.FusedAdam([pb], lr=LR, betas=(B1, B2), eps=EPS, weight_decay=1e-6)
+    opt_b.set_mask_source(lambda: {pb: (words, F)})
+
+    def both(seed):
+        g = (torch.randn((T, F), generator=torch.Generator().manual_seed(seed)) * 1e-2).to(DEV)
+        g[~keep] = 0                                           # a gradient never reaches the other rows
+        pa.grad, pb.grad = g, g.clone()
+        opt_a.step()
+        opt_b.step()
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        both(1)
+        both(2)
+        # (the masked entry point, and the kernel itself takes the group densely)
+        assert opt_b._last_call == "gngf_adam_step_masked" and not [w for w in caught if "reachable-row map" in str(w.message)]
+        assert float(opt_b.state[pb]["exp_avg"][~keep].abs().min()) > 0.0
+        for o in (opt_a, opt_b):
+            o.param_groups[0]["weight_decay"] = 0.0
+        both(3)
+        both(4)
+    said = [w for w in caught if "reachable-row map" in str(w.message)]
+    assert len(said) == 1 and opt_b._mask_source is None and opt_b._last_call == "gngf_adam_step"
+    assert float(opt_b._step) == 4.0
+    for k in ("exp_avg", "exp_avg_sq"):
+        assert bits_equal(opt_a.state[pa][k], opt_b.state[pb][k]), k
+    assert bits_equal(pa.detach(), pb.detach())
+    # (leaving those rows alone would not have been the dense result)
+    assert not bits_equal(opt_a.state[pa]["exp_avg"][~keep], torch.zeros_like(opt_a.state[pa]["exp_avg"][~keep]))
+
+
+def test_a_map_that_appears_after_dense_steps_is_checked_before_it_is_used():
+    """get_optimizer(..., skip_unreachable_rows=True) on a model with a trainable HPD steps densely (no map) and leaves moments
+    on whatever rows the per-batch tables used.  The HPD is then frozen (its weights changed once more: another table): the map
+    appears, and the dense step would go on moving rows outside it.  The first step that sees the map checks the moments, warns,
+    drops the map — and the optimizer stays bit for bit equal to the dense one."""
+    from collision_handling_in_instantngp_amd import models, train
+    assert not models.should_use_hash_function
+    T = 2048
+    torch.manual_seed(4)
+    net = models.GeneralNeuralGaugeFields(input_dim=2, hash_table_size=T, num_levels=4, n_min=4, n_max=32,
+                                          MLP_hidden_layers_widths=[64, 64], HPD_hidden_layers_widths=[32, 64, 128],
+                                          HPD_out_features=T, feature_dim=2, topk_k=4)
+    net.return_indices = False
+    net_b = copy.deepcopy(net)
+    opt = train.get_optimizer(net, 1e-2, 1e-3, 1e-3, 0.0, 0.0, 1e-6)
+    opt_b = train.get_optimizer(net_b, 1e-2, 1e-3, 1e-3, 0.0, 0.0, 1e-6, skip_unreachable_rows=True)
+    twin(opt, opt_b, net, net_b)
+    X, Y = batches_xy(2000, seed=9)
+    loss_fn = train.Loss(delta=1, gamma=-2, epsilon=1)
+    empty = torch.tensor([], device=DEV)
+
+    def step():
+        opt.zero_grad()
+        opt_b.zero_grad()
+        rgb, probs, _i, _c = net(X, 1.0)
+        mse, kls, coll = loss_fn(rgb, Y, None if probs is None else probs.shape[-1], probs, empty, empty)
+        train.assemble_loss(mse, kls, coll, 1, 1, 1e-3).backward()
+        opt.step()
+    step()
+    step()
+    assert opt_b._last_call == "gngf_adam_step" and opt_b._fits is None
+    gen = torch.Generator().manual_seed(12)
+    with torch.no_grad():
+        for p, q in zip(net.HPD.parameters(), net_b.HPD.parameters()):
+            d = (torch.randn(p.shape, generator=gen) * 0.5).to(DEV)
+            p.add_(d)
+            q.add_(d)
+    for n_ in (net, net_b):
+        for p in n_.HPD.parameters():
+            p.requires_grad = False
+        n_.dense_probs, n_.compute_pbar = False, False
+    rows = net_b.reachable_rows()
+    assert rows is not None
+    # the moments the dense steps left are not all inside the frozen table's map
+    w0 = net_b.encoding._hash_tables[0].weight
+    bits = torch.from_numpy(np.unpackbits(as_u32(rows[0]).view(np.uint8), bitorder="little")[:T].astype(bool)).to(DEV)
+    assert float(opt_b.state[w0]["exp_avg_sq"][~bits].abs().max()) > 0.0
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        step()
+        step()
+    said = [w for w in caught if "reachable-row map" in str(w.message)]
+    assert len(said) == 1 and opt_b._mask_source is None and opt_b._last_call == "gngf_adam_step"
+    assert float(opt_b._step) == 4.0
+    assert assert_same_state(net, net_b, opt, opt_b, "frozen after dense steps") > 0
+
+
+# ------------------------------------------------------------------------------------------------ 6. no map: the dense step
+@pytest.mark.parametrize("why", ["trainable_hpd", "batchnorm"])
+def test_models_without_a_fixed_row_set_give_no_map_and_step_densely(why):
+    from collision_handling_in_instantngp_amd import models, train
+    models.should_use_hash_function = why == "batchnorm"
+    models.should_batchnorm_data = why == "batchnorm"
+    try:
+        if why == "batchnorm":
+            net = hash_net(models, T=2048, L=4)
+        else:
+            torch.manual_seed(4)
+            net = models.GeneralNeuralGaugeFields(input_dim=2, hash_table_size=256, num_levels=4, n_min=4, n_max=32,
+                                                  MLP_hidden_layers_widths=[64, 64], HPD_hidden_layers_widths=[32, 64, 128],
+                                                  HPD_out_features=256, feature_dim=2, topk_k=4)
+            net.return_indices = False
+        assert net.reachable_rows() is None
+        net_b = copy.deepcopy(net)
+        opt = train.get_optimizer(net, 1e-2, 1e-3, 1e-3, 0.0, 0.0, 1e-6)
+        opt_b = train.get_optimizer(net_b, 1e-2, 1e-3, 1e-3, 0.0, 0.0, 1e-6, skip_unreachable_rows=True)
+        assert opt_b._mask_source is not None
+        twin(opt, opt_b, net, net_b)
+        X, Y = batches_xy(2000, seed=9)
+        loss_fn = train.Loss(delta=1, gamma=-2, epsilon=1)
+        empty = torch.tensor([], device=DEV)
+
+        def step():
+            opt.zero_grad()
+            rgb, probs, _i, _c = net(X, 1.0)
+            mse, kls, coll = loss_fn(rgb, Y, None if probs is None else probs.shape[-1], probs, empty, empty)
+            train.assemble_loss(mse, kls, coll, 1, 1, 1e-3).backward()
+            opt.step()
+        step()
+        step()
+        assert opt_b._last_call == "gngf_adam_step"
+        assert float(opt_b._step) == 2.0
+        assert assert_same_state(net, net_b, opt, opt_b, why) > 0
+        if why == "trainable_hpd":
+            # freezing the HPD (and asking for nothing that needs the per-batch table) gives the map
+            for p in net.HPD.parameters():
+                p.requires_grad = False
+            net.dense_probs, net.compute_pbar = False, False
+            assert net.reachable_rows() is not None
+            net.compute_pbar = True
+            assert net.reachable_rows() is None
+    finally:
+        models.should_batchnorm_data = False
+        models.should_use_hash_function = False
