@@ -367,10 +367,12 @@ class EncodeDirectFunction(torch.autograd.Function):
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
 
 
-def linear_fwd(x, w, b, act):
+def linear_fwd(x, w, b, act, y=None):
+    """y (M,N) = act(x w^T + b), into `y` where one is given."""
     M, K = x.shape
     N = w.shape[0]
-    y = torch.empty((M, N), dtype=_f32, device=x.device)
+    if y is None:
+        y = torch.empty((M, N), dtype=_f32, device=x.device)
     call("gngf_linear_fwd", ptr(x, _f32, "x"), ptr(w, _f32, "weight"), ptr(b, _f32, "bias"), ptr(y), M, N, K, act, stream_ptr())
     return y
 
@@ -532,6 +534,96 @@ class _split_gemm:
         return False
 
 
+def _hpd_epi(n, T, K, Hd):
+    """forward, per chunk: row statistics in the logits GEMM's epilogue — whole 128 x 128 tiles on the split-bf16 kernel"""
+    return (TUNING.hpd_epilogue_stats and TUNING.hpd_gemm_split_bf16 and n % 128 == 0 and T % 128 == 0 and Hd % 32 == 0
+            and K * 64 <= T and T < (1 << 22))
+
+
+def _hpd_fused(n, T, Lq, Kq, Hd):
+    """backward, per chunk: d-logits formed in the loaders of the dW / dh GEMMs (the ragged last chunk of a step is not)"""
+    return TUNING.hpd_bwd_fused and TUNING.hpd_gemm_split_bf16 and query("gngf_hpd_bwd_fused_applies", n, T, Lq, Kq, Hd) == 1
+
+
+class _ChunkPipe:
+    """Issues the stages A, B [, C] of the consecutive row chunks of one HPD pass; a stage is a function of the chunk's `args`.
+    A and C are the T-wide GEMMs (matrix-pipe bound), B the streaming passes over the logits (HBM bound).
+      in line (`skewed` False): A_i B_i C_i per chunk on the current stream, no events.
+      skewed over (main, side): A and C on main, B on side behind an event recorded after A; C_i is issued after A_{i+1} and
+        waits for B_i's event.  Main-stream order A_0 A_1 C_0 A_2 C_1 ... C_last: B_{i+1} runs beside C_i (or beside A_{i+2}).
+    A_{i+1} is issued while chunk i's logits are still being read, so in skewed mode the un-kept chunks alternate between TWO
+    logits buffers (checked below; in line one is enough).  In a pass with C a buffer's next A is issued on main behind the C that
+    last read it.  A pass without C names the alternating buffers a chunk uses (`rotating`): main waits, before the next A into
+    one of them, for the event recorded after the B that last read it.
+    The pass is in line when `skew` is off, a capture is in progress, the helper stream is the current one, or the second
+    logits buffer cannot be had (e.g. several processes sharing one device): one buffer means in line."""
+
+    def __init__(self, dev, skew, n_unkept, shape):
+        self.main = self.side = torch.cuda.current_stream(dev)
+        if skew and not torch.cuda.is_current_stream_capturing():
+            self.side = _side_stream(dev)
+        self.bufs = [torch.empty(shape, dtype=_f32, device=dev) for _ in range(min(1, n_unkept))]
+        if self.side.stream_id != self.main.stream_id and n_unkept > 1:
+            try:
+                self.bufs.append(torch.empty(shape, dtype=_f32, device=dev))
+            except torch.OutOfMemoryError:
+                self.side = self.main
+        self.skewed = self.side.stream_id != self.main.stream_id
+        if self.skewed and len(self.bufs) < min(2, n_unkept):
+            raise RuntimeError("skewed HPD chunks need two logits buffers")
+        self.n_unkept, self.free, self.pending, self.alive = 0, {}, None, []
+
+    def logits(self, n):
+        """the buffer of the next un-kept chunk (n rows)"""
+        self.n_unkept += 1
+        return self.bufs[(self.n_unkept - 1) % len(self.bufs)][:n]
+
+    def chunk(self, a, b, c, args, rotating=()):
+        """one chunk; `a` None: nothing to compute (logits kept), `c` None: the pass has no stage C"""
+        if not self.skewed:
+            for stage in (a, b, c):
+                if stage is not None:
+                    stage(*args)
+            return
+        main, side = self.main, self.side
+        for t in rotating:
+            if t.data_ptr() in self.free:
+                main.wait_event(self.free[t.data_ptr()])
+        if a is not None:
+            a(*args)
+        ready = torch.cuda.Event()
+        ready.record(main)
+        with torch.cuda.stream(side):
+            side.wait_event(ready)
+            b(*args)
+            done = torch.cuda.Event()
+            done.record(side)
+        self.alive.append(args)     # every tensor stays referenced until the join (the caching allocator knows only the allocating stream)
+        if c is None:
+            self.free.update((t.data_ptr(), done) for t in rotating)
+        self._issue_pending()       # C of the previous chunk, beside this chunk's B
+        if c is not None:
+            self.pending = (c, args, done)
+
+    def _issue_pending(self):
+        if self.pending is not None:
+            c, args, done = self.pending
+            self.main.wait_event(done)
+            c(*args)
+            self.pending = None
+
+    def join(self, both_ways=False, side_read=None):
+        """end of the pass.  both_ways: the helper's next use starts behind everything issued here; side_read: what it read last"""
+        if self.skewed:
+            self._issue_pending()
+            self.main.wait_stream(self.side)
+            if both_ways:
+                self.side.wait_stream(self.main)
+            if side_read is not None:
+                side_read.record_stream(self.side)
+            del self.alive[:]
+
+
 class HpdVertexFunction(torch.autograd.Function):
     """HashProbDistribution (reference models.py:45-123) evaluated ONCE PER DISTINCT VERTEX u (vid = gy*vstride+gx,
     u in [0, NV)), in row chunks so that the (rows, T) distribution never exceeds `chunk_bytes`.
@@ -541,7 +633,9 @@ class HpdVertexFunction(torch.autograd.Function):
     pbar_l = sum_u mw[u,l] * probs[u]  is the batch-mean distribution of utils.py:138,159 (mw = multiplicity/(4P)).
     Backward recomputes each chunk (hidden layers, logits, softmax) and folds the top-K gradient and the
     low-rank p-bar gradient into the softmax backward: the dense (P,L,4,T) zero-filled scatter of
-    models.py:27-35 never exists."""
+    models.py:27-35 never exists.
+    Both passes hand their per-chunk stages to one _ChunkPipe; the dense distribution (keep_probs, or a dense gradient on it: small
+    shapes) has stages of its own and runs in line."""
 
     @staticmethod
     def _hidden(verts, params, n_layers):
@@ -551,32 +645,30 @@ class HpdVertexFunction(torch.autograd.Function):
         return hs
 
     @staticmethod
+    def _logits(h, W, b, z):
+        with _split_gemm():
+            linear_fwd(h, W, b, ACT_NONE, y=z)
+
+    @staticmethod
     def forward(ctx, NV, vstride, K, mw, keep_probs, chunk_bytes, aux, *params):
         params = tuple(_c(p) for p in params)
         n_layers = len(params) // 2
         W_last, b_last = params[-2], params[-1]
-        T = W_last.shape[0]
+        T, Hd = W_last.shape
         dev = W_last.device
         rows = int(max(64, min(NV, chunk_bytes // (4 * T))))
+        n_chunks = -(-NV // rows)
         tv = torch.empty((NV, K), dtype=_f32, device=dev)
         ti = torch.empty((NV, K), dtype=_i32, device=dev)
         rowstat = torch.empty((NV, 2), dtype=_f32, device=dev)
         probs = torch.empty((NV, T), dtype=_f32, device=dev) if keep_probs else None
-        pbar = None
+        pbar, L = None, 0
         if mw is not None:
             mw = _c(mw)
             L = mw.shape[1]
             pbar = torch.zeros((L, T), dtype=_f32, device=dev)
-        pipelined = (TUNING.hpd_pipeline and TUNING.hpd_pipeline_fwd and not keep_probs and NV > rows
-                     and not torch.cuda.is_current_stream_capturing())
-        main = torch.cuda.current_stream(dev)
-        side = _side_stream(dev) if pipelined else None
-        pipelined = pipelined and side is not main and side.stream_id != main.stream_id
-        # un-kept chunks alternate between two logits buffers when pipelined (the passes of chunk i read one while the GEMM
-        # of chunk i + 1 fills the other)
-        scratch = None if keep_probs else [torch.empty((min(rows, NV), T), dtype=_f32, device=dev) for _ in range(2 if pipelined else 1)]
-        scratch_free = [None] * (len(scratch) if scratch else 0)      # event after the last pass that read the buffer
-        n_scratch = 0
+        pipe = _ChunkPipe(dev, TUNING.hpd_pipeline and TUNING.hpd_pipeline_fwd and not keep_probs and NV > rows,
+                          0 if keep_probs else n_chunks, (min(rows, NV), T))
         # Checkpointing policy sized for 288 GB of HBM: the backward needs every chunk's logits again; the chunks that fit
         # HPD_Z_CACHE_BYTES (and leave HPD_Z_CACHE_RESERVE free on the device) keep theirs, the rest are recomputed.
         zcache, cached = {}, 0
@@ -587,19 +679,42 @@ class HpdVertexFunction(torch.autograd.Function):
         # microseconds of work each, and a small launch that has to find free CUs beside a 5 ms streaming pass on the helper
         # stream takes 0.2-0.4 ms — 108 ms of a 890 ms step at 44 chunks (profiles/r03_kernel_stats_gngf_learning.txt).
         hs_all = HpdVertexFunction._hidden(vertex_coords(0, NV, vstride, dev), params, n_layers)
+        h_last = hs_all[-1]
         if keep_z:
             # one query per forward: memory the driver reports free plus what torch's allocator holds in unused cached blocks
             # (the previous step's kept chunks come back from there), minus the reserve for the backward's own buffers.  Taken
             # AFTER the hidden layers of all NV vertices are allocated (they live until the backward pass), and less the backward's
             # dH (NV x last hidden width): ~1.5 GB at a million vertices that the budget used to hand to the logits
             free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-            budget = min(TUNING.hpd_z_cache_bytes, free - TUNING.hpd_z_cache_reserve - NV * W_last.shape[1] * 4)
-        parts, parts_free, n_parts = None, None, 0          # row partials of the GEMM epilogue (two buffers when pipelined)
-        L = mw.shape[1] if mw is not None else 0
+            budget = min(TUNING.hpd_z_cache_bytes, free - TUNING.hpd_z_cache_reserve - NV * Hd * 4)
+        parts, n_parts = None, 0          # row partials of the GEMM epilogue (alternating, as the logits buffers)
+
+        def stage_a(u0, n, z, part):
+            if part is not None:
+                call("gngf_linear_fwd_rowstats", ptr(h_last[u0:u0 + n]), ptr(W_last), ptr(b_last), ptr(z), ptr(part), n, T, Hd, stream_ptr())
+            else:
+                HpdVertexFunction._logits(h_last[u0:u0 + n], W_last, b_last, z)
+
+        def stage_b(u0, n, z, part):       # the logits are only read: stats + top-K in one pass — or from the GEMM's partials —, p-bar in a second
+            s = slice(u0, u0 + n)
+            if part is not None:
+                call("gngf_rowstats_topk", ptr(z), ptr(part), ptr(tv[s]), ptr(ti[s]), ptr(rowstat[s]), n, T, K, stream_ptr())
+                if pbar is not None:
+                    call("gngf_pbar_accumulate", ptr(z), ptr(rowstat[s]), ptr(mw[s]), L, ptr(pbar), n, T, stream_ptr())
+            else:
+                call("gngf_logits_topk_pbar", ptr(z), ptr(tv[s]), ptr(ti[s]), ptr(rowstat[s]), ptr(mw[s] if pbar is not None else None),
+                     L if pbar is not None else 0, ptr(pbar), n, T, K, stream_ptr())
+
+        def dense(u0, n):                  # dense distribution requested: softmax in place, p-bar by GEMM
+            s = slice(u0, u0 + n)
+            stage_a(u0, n, probs[s], None)
+            call("gngf_softmax_topk", ptr(probs[s]), ptr(tv[s]), ptr(ti[s]), ptr(rowstat[s]), n, T, K, stream_ptr())
+            if pbar is not None:
+                gemm_acc(mw[s], probs[s], pbar, L, T, n, ta=True, tb=False)
+
         for u0 in range(0, NV, rows):
             n = min(rows, NV - u0)
-            hs = [h[u0:u0 + n] for h in hs_all]
-            z = probs[u0:u0 + n] if keep_probs else None
+            z = None
             if keep_z:
                 need = n * T * 4
                 if cached + need <= budget:
@@ -608,65 +723,28 @@ class HpdVertexFunction(torch.autograd.Function):
                         cached += need
                     except torch.OutOfMemoryError:      # another process took the memory meanwhile: recompute from here on
                         budget = 0
-            sb = None
+            epi = not keep_probs and _hpd_epi(n, T, K, Hd)
+            _trace("hpd_chunk", pass_="fwd", u0=u0, n=n, epi=epi, kept=u0 in zcache, fused=False, pipelined=pipe.skewed)
+            if keep_probs:
+                dense(u0, n)
+                continue
+            rotating = []
             if z is None:
-                sb = n_scratch % len(scratch)
-                n_scratch += 1
-                z = scratch[sb][:n]
-                if scratch_free[sb] is not None:
-                    main.wait_event(scratch_free[sb])
-            # statistics in the GEMM's epilogue when the chunk is whole 128 x 128 tiles on the split-bf16 kernel
-            epi = (TUNING.hpd_epilogue_stats and TUNING.hpd_gemm_split_bf16 and not keep_probs and n % 128 == 0 and T % 128 == 0
-                   and W_last.shape[1] % 32 == 0 and K * 64 <= T and T < (1 << 22))
+                z = pipe.logits(n)
+                rotating.append(z)
+            part = None
             if epi:
                 if parts is None:
-                    parts = [torch.empty((min(rows, NV), T // 64, 2), dtype=_f32, device=dev) for _ in range(2 if pipelined else 1)]
-                    parts_free = [None] * len(parts)
-                pb = n_parts % len(parts)
+                    parts = [torch.empty((min(rows, NV), T // 64, 2), dtype=_f32, device=dev) for _ in range(2 if pipe.skewed else 1)]
+                part = parts[n_parts % len(parts)]
                 n_parts += 1
-                if parts_free[pb] is not None:
-                    main.wait_event(parts_free[pb])
-                call("gngf_linear_fwd_rowstats", ptr(hs[-1]), ptr(W_last), ptr(b_last), ptr(z), ptr(parts[pb]), n, T, W_last.shape[1],
-                     stream_ptr())
-            else:
-                with _split_gemm():
-                    call("gngf_linear_fwd", ptr(hs[-1]), ptr(W_last), ptr(b_last), ptr(z), n, T, W_last.shape[1], ACT_NONE, stream_ptr())
-
-            def passes():
-                if epi:
-                    call("gngf_rowstats_topk", ptr(z), ptr(parts[pb]), ptr(tv[u0:u0 + n]), ptr(ti[u0:u0 + n]), ptr(rowstat[u0:u0 + n]),
-                         n, T, K, stream_ptr())
-                    if pbar is not None:
-                        call("gngf_pbar_accumulate", ptr(z), ptr(rowstat[u0:u0 + n]), ptr(mw[u0:u0 + n]), L, ptr(pbar), n, T, stream_ptr())
-                else:
-                    call("gngf_logits_topk_pbar", ptr(z), ptr(tv[u0:u0 + n]), ptr(ti[u0:u0 + n]), ptr(rowstat[u0:u0 + n]),
-                         ptr(mw[u0:u0 + n] if pbar is not None else None), L if pbar is not None else 0, ptr(pbar), n, T, K, stream_ptr())
-            _trace("hpd_chunk", pass_="fwd", u0=u0, n=n, epi=epi, kept=u0 in zcache, fused=False, pipelined=pipelined)
-            if pipelined:
-                ready = torch.cuda.Event()
-                ready.record(main)
-                with torch.cuda.stream(side):
-                    side.wait_event(ready)
-                    passes()
-                    if sb is not None:
-                        scratch_free[sb] = torch.cuda.Event()
-                        scratch_free[sb].record(side)
-                    if epi:
-                        parts_free[pb] = torch.cuda.Event()
-                        parts_free[pb].record(side)
-                continue
-            if keep_probs:      # dense distribution requested (small shapes): softmax in place, p-bar by GEMM
-                call("gngf_softmax_topk", ptr(z), ptr(tv[u0:u0 + n]), ptr(ti[u0:u0 + n]), ptr(rowstat[u0:u0 + n]), n, T, K, stream_ptr())
-                if pbar is not None:
-                    gemm_acc(mw[u0:u0 + n], z, pbar, L, T, n, ta=True, tb=False)
-            else:               # streaming: the logits are only read (stats + top-K in one pass — or from the GEMM's partials —, p-bar in a second)
-                passes()
-        if pipelined:
-            main.wait_stream(side)
+                rotating.append(part)
+            pipe.chunk(stage_a, stage_b, None, (u0, n, z, part), rotating)
+        pipe.join()
         if pbar is not None and aux is not None and aux.mean is not None:
             aux.mean(pbar)     # the loss is a nonlinear function of the batch mean: average BEFORE the log (SURVEY §8e ii)
         if aux is not None and aux.stats is not None:
-            aux.stats.update(rows_total=int(NV), T=int(T), rows_per_chunk=int(rows), chunks=-(-NV // rows), chunks_kept=len(zcache))
+            aux.stats.update(rows_total=int(NV), T=int(T), rows_per_chunk=int(rows), chunks=n_chunks, chunks_kept=len(zcache))
         ctx.cfg = (NV, vstride, K, rows, n_layers, T, keep_probs)
         ctx.zcache = zcache
         ctx.hidden = hs_all if any(ctx.needs_input_grad[7:]) else None      # activations of every vertex (no recomputation in backward)
@@ -680,95 +758,85 @@ class HpdVertexFunction(torch.autograd.Function):
         ti, mw, probs, rowstat, tv = ctx.saved_tensors[:5]
         params = ctx.saved_tensors[5:]
         W_last, b_last = params[-2], params[-1]
+        Hd = W_last.shape[1]
         dev = W_last.device
         grads = [torch.zeros_like(p) for p in params]
+        dW, db = grads[-2], grads[-1]
         hs_all, ctx.hidden = getattr(ctx, "hidden", None), None
         if hs_all is None:
             hs_all = HpdVertexFunction._hidden(vertex_coords(0, NV, vstride, dev), params, n_layers)
-        dH = torch.zeros((NV, W_last.shape[1]), dtype=_f32, device=dev)       # d loss / d (last hidden layer), every vertex
+        h_last = hs_all[-1]
+        dH = torch.zeros((NV, Hd), dtype=_f32, device=dev)       # d loss / d (last hidden layer), every vertex
         g_tv = _c(g_tv) if g_tv is not None else None
         g_pbar = _c(g_pbar) if (g_pbar is not None and mw is not None) else None
         g_probs = _c(g_probs) if g_probs is not None else None
         L = mw.shape[1] if mw is not None else 0
+        Lq, Kq = (L if g_pbar is not None else 0), (K if g_tv is not None else 0)
         lowrank = g_probs is None           # no dense gradient on the distribution: stream from (kept or recomputed) logits
         zcache, ctx.zcache = (getattr(ctx, "zcache", None) or {}), None
         if not lowrank:
             zcache = {}
-        dz_buf = None
+        # the whole chunks and the ragged last one differ in size: either of them may be the fused one
+        fused = {n: lowrank and _hpd_fused(n, T, Lq, Kq, Hd) for n in {min(rows, NV - u0) for u0 in range(0, NV, rows)}}
+        pipe = _ChunkPipe(dev, TUNING.hpd_pipeline and lowrank and NV > rows, -(-NV // rows) - len(zcache), (min(rows, NV), T))
         if lowrank:
-            scratch = torch.empty((min(rows, NV) * (1 + K),), dtype=_f32, device=dev)
-        pipelined = TUNING.hpd_pipeline and lowrank and NV > rows and not torch.cuda.is_current_stream_capturing()
-        main = torch.cuda.current_stream(dev)
-        side = _side_stream(dev) if pipelined else None
-        pipelined = pipelined and side.stream_id != main.stream_id
-        if pipelined:
-            # un-kept chunks alternate between TWO logits buffers; without the memory for both (e.g. several processes sharing
-            # one device) the chunks run one after the other as before
-            n_chunks = -(-NV // rows)
-            dz_bufs = []
-            try:
-                for _ in range(min(2, n_chunks - len(zcache))):
-                    dz_bufs.append(torch.empty((min(rows, NV), T), dtype=_f32, device=dev))
-            except torch.OutOfMemoryError:
-                pipelined = False
-                dz_buf = dz_bufs[0] if dz_bufs else None
-                dz_bufs = None
-        if pipelined:
-            HpdVertexFunction._backward_pipelined(ctx.cfg, ti, mw, rowstat, tv, params, grads, g_tv, g_pbar, L, zcache, scratch, main, side,
-                                                  dz_bufs, hs_all, dH)
-            HpdVertexFunction._hidden_backward(hs_all, dH, params, grads, n_layers)
-            return (None, None, None, None, None, None, None, *grads)
-        prep_serial = None
-        Lq, Kq = (L if g_pbar is not None else 0), (K if g_tv is not None else 0)
+            work = torch.empty((min(rows, NV) * (1 + K),), dtype=_f32, device=dev)      # of gngf_softmax_bwd_lowrank
+            # the small operands as bf16 planes, once per pass, and the row dots of every chunk (the GEMMs of chunk i read them while
+            # the dot pass of chunk i + 1 writes its own)
+            prep = _HpdBwdPlanes(h_last, mw, W_last, g_pbar, Lq, 2 if TUNING.hpd_bwd_two_planes else 3) if any(fused.values()) else None
+            dots = torch.empty((NV,), dtype=_f32, device=dev) if prep is not None else None
+
+        def stage_a(u0, n, dz):            # logits again (a kept chunk has no A)
+            HpdVertexFunction._logits(h_last[u0:u0 + n], W_last, b_last, dz)
+
+        def stage_b(u0, n, dz):
+            s = slice(u0, u0 + n)
+            if fused[n]:                   # one read of the logits: the row dots only
+                call("gngf_hpd_bwd_dot", ptr(dz), ptr(rowstat[s]), ptr(g_tv[s] if Kq else None), ptr(tv[s] if Kq else None),
+                     ptr(mw[s] if Lq else None), ptr(g_pbar if Lq else None), Lq, ptr(dots[s]), n, T, Kq, stream_ptr())
+            else:                          # softmax / top-K / batch-mean backward in place; db of the last layer is fused in
+                call("gngf_softmax_bwd_lowrank", ptr(dz), ptr(rowstat[s]), ptr(g_tv[s] if g_tv is not None else None), ptr(ti[s]),
+                     ptr(mw[s] if g_pbar is not None else None), ptr(g_pbar), Lq, ptr(db), ptr(work),
+                     ptr(tv[s] if g_tv is not None else None), n, T, Kq, stream_ptr())
+
+        def stage_c(u0, n, dz):
+            s = slice(u0, u0 + n)
+            if fused[n]:                   # dz formed in the loaders of both GEMMs, which read the logits (dz IS the logits here)
+                prep.fused(dz, rowstat[s], dots[s], g_tv[s] if Kq else None, tv[s] if Kq else None, ti[s] if Kq else None,
+                           h_last[s], W_last, dW, db, dH[s], u0, n, T, Kq)
+            else:
+                with _split_gemm(accumulating=True):
+                    linear_bwd_weight(dz, None, h_last[s], dW, None, ACT_NONE)
+                    gemm_acc(dz, W_last, dH[s], n, Hd, T, ta=False, tb=False)     # dh = dz @ W_last, split over T
+
+        def dense(u0, n, dz):              # a dense gradient on the distribution: d-logits by the dense softmax backward
+            s = slice(u0, u0 + n)
+            if keep_probs:
+                p_chunk = probs[s]
+            else:   # recompute logits + softmax in the scratch (top-K indices are the saved ones)
+                linear_fwd(h_last[s], W_last, b_last, ACT_NONE, y=dz)
+                tv_tmp = torch.empty((n, K), dtype=_f32, device=dev)
+                ti_tmp = torch.empty((n, K), dtype=_i32, device=dev)
+                call("gngf_softmax_topk", ptr(dz), ptr(tv_tmp), ptr(ti_tmp), ptr(None), n, T, K, stream_ptr())
+                p_chunk = dz
+            call("gngf_softmax_bwd", ptr(p_chunk), ptr(g_tv[s] if g_tv is not None else None), ptr(ti[s]), ptr(g_probs[s]),
+                 ptr(mw[s] if g_pbar is not None else None), ptr(g_pbar), L, ptr(dz), n, T, Kq, stream_ptr())
+            linear_bwd_weight(dz, None, h_last[s], dW, db, ACT_NONE)
+            with _split_gemm():
+                gemm_acc(dz, W_last, dH[s], n, Hd, T, ta=False, tb=False)
+
         for u0 in range(0, NV, rows):
             n = min(rows, NV - u0)
-            hs = [h[u0:u0 + n] for h in hs_all]
-            dz = zcache.pop(u0, None)       # this chunk's logits, kept by the forward (freed as soon as the chunk is done)
-            have_z = dz is not None
-            if not have_z:
-                if dz_buf is None:
-                    dz_buf = torch.empty((min(rows, NV), T), dtype=_f32, device=dev)
-                dz = dz_buf[:n]
-            fused = (lowrank and TUNING.hpd_bwd_fused and TUNING.hpd_gemm_split_bf16
-                     and query("gngf_hpd_bwd_fused_applies", n, T, Lq, Kq, W_last.shape[1]) == 1)
-            _trace("hpd_chunk", pass_="bwd", u0=u0, n=n, epi=False, kept=have_z, fused=fused, pipelined=False)
+            dz = zcache.pop(u0, None)       # this chunk's logits, kept by the forward (in line: freed as soon as the chunk is done)
+            kept = dz is not None
+            _trace("hpd_chunk", pass_="bwd", u0=u0, n=n, epi=False, kept=kept, fused=fused[n], pipelined=pipe.skewed)
+            if not kept:
+                dz = pipe.logits(n)
             if lowrank:
-                # logits (again, unless kept), then softmax / top-K / batch-mean backward in place; db of the last layer is fused in
-                if not have_z:
-                    with _split_gemm():
-                        call("gngf_linear_fwd", ptr(hs[-1]), ptr(W_last), ptr(b_last), ptr(dz), n, T, W_last.shape[1], ACT_NONE, stream_ptr())
-                if fused:
-                    if prep_serial is None:
-                        prep_serial = _HpdBwdPlanes(hs_all[-1], mw, W_last, g_pbar, Lq, 2 if TUNING.hpd_bwd_two_planes else 3)
-                    dotv = scratch[:n]
-                    call("gngf_hpd_bwd_dot", ptr(dz), ptr(rowstat[u0:u0 + n]), ptr(g_tv[u0:u0 + n] if Kq else None),
-                         ptr(tv[u0:u0 + n] if Kq else None), ptr(mw[u0:u0 + n] if Lq else None), ptr(g_pbar if Lq else None), Lq,
-                         ptr(dotv), n, T, Kq, stream_ptr())
-                    prep_serial.fused(dz, rowstat[u0:u0 + n], dotv, g_tv[u0:u0 + n] if Kq else None, tv[u0:u0 + n] if Kq else None,
-                                      ti[u0:u0 + n] if Kq else None, hs[-1], W_last, grads[-2], grads[-1], dH[u0:u0 + n], u0, n, T, Kq)
-                    continue
-                call("gngf_softmax_bwd_lowrank", ptr(dz), ptr(rowstat[u0:u0 + n]),
-                     ptr(g_tv[u0:u0 + n] if g_tv is not None else None), ptr(ti[u0:u0 + n]),
-                     ptr(mw[u0:u0 + n] if g_pbar is not None else None), ptr(g_pbar), L if g_pbar is not None else 0,
-                     ptr(grads[-1]), ptr(scratch), ptr(tv[u0:u0 + n] if g_tv is not None else None), n, T,
-                     K if g_tv is not None else 0, stream_ptr())
-                with _split_gemm(accumulating=True):
-                    linear_bwd_weight(dz, None, hs[-1], grads[-2], None, ACT_NONE)
+                pipe.chunk(None if kept else stage_a, stage_b, stage_c, (u0, n, dz))
             else:
-                if keep_probs:
-                    p_chunk = probs[u0:u0 + n]
-                else:   # recompute logits + softmax in the scratch (top-K indices are the saved ones)
-                    call("gngf_linear_fwd", ptr(hs[-1]), ptr(W_last), ptr(b_last), ptr(dz), n, T, W_last.shape[1], ACT_NONE, stream_ptr())
-                    tv_tmp = torch.empty((n, K), dtype=_f32, device=dev)
-                    ti_tmp = torch.empty((n, K), dtype=_i32, device=dev)
-                    call("gngf_softmax_topk", ptr(dz), ptr(tv_tmp), ptr(ti_tmp), ptr(None), n, T, K, stream_ptr())
-                    p_chunk = dz
-                call("gngf_softmax_bwd", ptr(p_chunk), ptr(g_tv[u0:u0 + n] if g_tv is not None else None), ptr(ti[u0:u0 + n]),
-                     ptr(g_probs[u0:u0 + n]), ptr(mw[u0:u0 + n] if g_pbar is not None else None), ptr(g_pbar), L, ptr(dz), n, T,
-                     K if g_tv is not None else 0, stream_ptr())
-                linear_bwd_weight(dz, None, hs[-1], grads[-2], grads[-1], ACT_NONE)
-            with _split_gemm(accumulating=lowrank):
-                gemm_acc(dz, W_last, dH[u0:u0 + n], n, W_last.shape[1], T, ta=False, tb=False)     # dh = dz @ W_last, split over T
+                dense(u0, n, dz)
+        pipe.join(both_ways=True, side_read=dots if lowrank else None)
         HpdVertexFunction._hidden_backward(hs_all, dH, params, grads, n_layers)
         return (None, None, None, None, None, None, None, *grads)
 
@@ -780,81 +848,6 @@ class HpdVertexFunction(torch.autograd.Function):
             linear_bwd_weight(g, hs_all[i + 1], hs_all[i], grads[2 * i], grads[2 * i + 1], ACT_RELU)
             if i > 0:
                 g = linear_bwd_input(g, hs_all[i + 1], params[2 * i], ACT_RELU)
-
-    @staticmethod
-    def _backward_pipelined(cfg, ti, mw, rowstat, tv, params, grads, g_tv, g_pbar, L, zcache, scratch, main, side, dz_bufs, hs_all, dH):
-        """The low-rank backward with its chunks software-pipelined over two streams.  Per chunk: A (main) logits again unless
-        kept; B (side) softmax / top-K / batch-mean backward in place, HBM bound; C (main) the dW and dh GEMMs and the small
-        layers, matrix-pipe bound.  Issue order on main: A_0, A_1, C_0, A_2, C_1, ... so that C_i runs beside B_{i+1}.  Un-kept
-        chunks alternate between two logits buffers; a buffer's next A is issued on main behind the C that last read it.
-        Every tensor stays referenced until both streams have joined (the caching allocator knows only the allocating stream)."""
-        NV, vstride, K, rows, n_layers, T, _keep = cfg
-        W_last, b_last = params[-2], params[-1]
-        dev = W_last.device
-        n_unkept, alive, pending = 0, [], None
-        Lq = L if g_pbar is not None else 0
-        Kq = K if g_tv is not None else 0
-        planes = 2 if TUNING.hpd_bwd_two_planes else 3
-        dots = torch.empty((NV,), dtype=_f32, device=dev) if TUNING.hpd_bwd_fused else None    # row dots of every chunk (the GEMMs of chunk i read
-        #                                                                                       them while the dot pass of chunk i + 1 writes its own)
-
-        def fused(n):
-            return (TUNING.hpd_bwd_fused and TUNING.hpd_gemm_split_bf16
-                    and query("gngf_hpd_bwd_fused_applies", n, T, Lq, Kq, W_last.shape[1]) == 1)
-        # the whole chunks and the ragged last one differ in size: either of them may be the fused one
-        sizes = {min(rows, NV - u0) for u0 in range(0, NV, rows)}
-        prep = (_HpdBwdPlanes(hs_all[-1], mw, W_last, g_pbar, Lq, planes) if any(fused(n) for n in sizes) else None)
-
-        def stage_b(dz, n, u0):
-            if fused(n):          # one read of the logits: the row dots only
-                call("gngf_hpd_bwd_dot", ptr(dz), ptr(rowstat[u0:u0 + n]), ptr(g_tv[u0:u0 + n] if Kq else None),
-                     ptr(tv[u0:u0 + n] if Kq else None), ptr(mw[u0:u0 + n] if Lq else None), ptr(g_pbar if Lq else None), Lq,
-                     ptr(dots[u0:u0 + n]), n, T, Kq, stream_ptr())
-                return
-            call("gngf_softmax_bwd_lowrank", ptr(dz), ptr(rowstat[u0:u0 + n]),
-                 ptr(g_tv[u0:u0 + n] if g_tv is not None else None), ptr(ti[u0:u0 + n]),
-                 ptr(mw[u0:u0 + n] if g_pbar is not None else None), ptr(g_pbar), L if g_pbar is not None else 0,
-                 ptr(grads[-1]), ptr(scratch), ptr(tv[u0:u0 + n] if g_tv is not None else None), n, T,
-                 K if g_tv is not None else 0, stream_ptr())
-
-        def stage_c(dz, hs, done_b, n, u0):
-            main.wait_event(done_b)
-            if fused(n):          # dz formed in the loaders of both GEMMs, which read the logits (dz IS the logits here)
-                prep.fused(dz, rowstat[u0:u0 + n], dots[u0:u0 + n], g_tv[u0:u0 + n] if Kq else None, tv[u0:u0 + n] if Kq else None,
-                           ti[u0:u0 + n] if Kq else None, hs[-1], W_last, grads[-2], grads[-1], dH[u0:u0 + n], u0, n, T, Kq)
-                return
-            with _split_gemm(accumulating=True):
-                linear_bwd_weight(dz, None, hs[-1], grads[-2], None, ACT_NONE)
-                gemm_acc(dz, W_last, dH[u0:u0 + n], n, W_last.shape[1], T, ta=False, tb=False)     # dh = dz @ W_last, split over T
-
-        for u0 in range(0, NV, rows):
-            n = min(rows, NV - u0)
-            hs = [h[u0:u0 + n] for h in hs_all]
-            dz = zcache.pop(u0, None)
-            _trace("hpd_chunk", pass_="bwd", u0=u0, n=n, epi=False, kept=dz is not None, fused=fused(n), pipelined=True)
-            if dz is None:                                     # A: not kept by the forward
-                dz = dz_bufs[n_unkept % len(dz_bufs)][:n]
-                n_unkept += 1
-                with _split_gemm():
-                    call("gngf_linear_fwd", ptr(hs[-1]), ptr(W_last), ptr(b_last), ptr(dz), n, T, W_last.shape[1], ACT_NONE, stream_ptr())
-            alive.extend([dz, hs])
-            ready = torch.cuda.Event()
-            ready.record(main)
-            with torch.cuda.stream(side):                      # B
-                side.wait_event(ready)
-                stage_b(dz, n, u0)
-                done_b = torch.cuda.Event()
-                done_b.record(side)
-            if pending is not None:                            # C of the previous chunk, beside this chunk's B
-                stage_c(*pending)
-            pending = (dz, hs, done_b, n, u0)
-        if pending is not None:
-            stage_c(*pending)
-        main.wait_stream(side)
-        side.wait_stream(main)       # the helper's next use starts behind everything issued here
-        if dots is not None:
-            dots.record_stream(side)
-        del alive[:]
 
 
 class BlendFunction(torch.autograd.Function):

@@ -520,3 +520,107 @@ def test_ties_go_to_the_lower_index(ops):
                 if t_ >= h:
                     assert t_ - h in s, row
         check_values(name, r, f"L ties {tun.hpd_epilogue_stats}/{tun.hpd_gemm_split_bf16}")
+
+
+# ------------------------------------------------------------------------------------------------ issue order and streams
+# position of the rows argument of every per-chunk entry point (include/gngf.h)
+ROWS_ARG = {"gngf_linear_fwd": 4, "gngf_linear_fwd_rowstats": 5, "gngf_rowstats_topk": 5, "gngf_pbar_accumulate": 5,
+            "gngf_logits_topk_pbar": 7, "gngf_hpd_bwd_dot": 8, "gngf_softmax_bwd_lowrank": 10, "gngf_hpd_bwd_fused": 16,
+            "gngf_linear_bwd_weight": 5, "gngf_gemm_acc": 3}
+SIDE_FWD = {"gngf_rowstats_topk", "gngf_pbar_accumulate", "gngf_logits_topk_pbar"}
+SIDE_BWD = {"gngf_hpd_bwd_dot", "gngf_softmax_bwd_lowrank"}
+
+
+def _is_stage(name, args, T):
+    """is this launch a per-chunk stage (a T-wide product or a pass over the logits), not a hidden layer of all vertices?"""
+    if name not in ROWS_ARG:
+        return False
+    wide = {"gngf_linear_fwd": 5, "gngf_linear_bwd_weight": 6, "gngf_gemm_acc": 5}       # N, N, Kc
+    return name not in wide or args[wide[name]] == T
+
+
+def _stages(case, tun, rec):
+    """what each chunk issues, stage by stage, from the documented dispatch rules: [(A, B, C)] per pass, lists of (entry, rows)"""
+    nch = len(case.chunks)
+    fwd, bwd = [], []
+    for w, got in zip(expected_trace(case, tun), rec):
+        n = w["n"]
+        if w["pass_"] == "fwd":
+            b = ["gngf_rowstats_topk"] + ["gngf_pbar_accumulate"] * bool(case.L) if w["epi"] else ["gngf_logits_topk_pbar"]
+            fwd.append(([("gngf_linear_fwd_rowstats" if w["epi"] else "gngf_linear_fwd", n)], [(e, n) for e in b], []))
+        else:
+            c = ["gngf_hpd_bwd_fused"] if w["fused"] else ["gngf_linear_bwd_weight", "gngf_gemm_acc"]
+            bwd.append(([] if got["kept"] else [("gngf_linear_fwd", n)],
+                        [("gngf_hpd_bwd_dot" if w["fused"] else "gngf_softmax_bwd_lowrank", n)], [(e, n) for e in c]))
+    assert len(fwd) == len(bwd) == nch
+    return fwd, bwd
+
+
+def _check_issue_order(case, tun, mode, trace, log):
+    """log: (entry, rows or None, on the main stream?) per launch, with a ("backward", None, True) mark between the passes"""
+    cut = log.index(("backward", None, True))
+    passes = {"fwd": log[:cut], "bwd": log[cut + 1:]}
+    stages = dict(zip(("fwd", "bwd"), _stages(case, tun, trace)))
+    any_fused = any(t["fused"] for t in trace)
+    assert [e for e, _, _ in log].count("gngf_hpd_bwd_prepare") == [e for e, _, _ in passes["bwd"]].count("gngf_hpd_bwd_prepare") \
+        == int(any_fused)
+    for ps, side_set in (("fwd", SIDE_FWD), ("bwd", SIDE_BWD)):
+        got = [(e, n, m) for e, n, m in passes[ps] if n is not None]
+        assert all(m for e, n, m in passes[ps] if n is None), passes[ps]           # hidden layers, planes: main stream
+        if mode == "default":
+            assert all(t["pipelined"] for t in trace)
+            assert {e for e, _, m in got if not m} == {e for _, b, _ in stages[ps] for e, _ in b} <= side_set
+            assert all((e in side_set) == (not m) for e, _, m in got), got
+            want_side = [x for _, b, _ in stages[ps] for x in b]
+            want_main, prev = [], []
+            for a, _, c in stages[ps]:
+                want_main += a + prev
+                prev = c
+            want_main += prev
+            assert [(e, n) for e, n, m in got if not m] == want_side
+            assert [(e, n) for e, n, m in got if m] == want_main
+        else:
+            assert not any(t["pipelined"] for t in trace)
+            assert all(m for _, _, m in got), got
+            assert [(e, n) for e, n, _ in got] == [x for a, b, c in stages[ps] for x in a + b + c]
+
+
+ORDER_RUNS = {
+    # z-cache off: every chunk of the backward pass has its A, whatever memory the device has free
+    "B": ("B", dict(hpd_z_cache_bytes=0)),
+    "D": ("D", dict(hpd_z_cache_bytes=0)),
+    # the first chunk's logits are kept: it has no A in the backward pass
+    "B_first_kept": ("B", dict(hpd_z_cache_bytes=CASES["B"].rows_eff * CASES["B"].T * 4, hpd_z_cache_reserve=0)),
+}
+
+
+@pytest.mark.parametrize("mode", ["default", "no_pipeline", "no_side_stream"])
+@pytest.mark.parametrize("which", list(ORDER_RUNS))
+def test_stages_are_issued_in_the_documented_order_on_the_documented_stream(ops, monkeypatch, which, mode):
+    """Default tuning: A and C on the main stream in the order A0 A1 C0 A2 C1 ... C_last (a kept chunk has no A), B on the helper
+    stream and nothing else there; gngf_hpd_bwd_prepare once per backward pass with a fused chunk, never otherwise.
+    hpd_pipeline=False / use_side_stream=False: everything on the main stream, A_i B_i C_i per chunk."""
+    name, kw = ORDER_RUNS[which]
+    case = CASES[name]
+    kw = dict(kw, **{"default": {}, "no_pipeline": dict(hpd_pipeline=False), "no_side_stream": dict(use_side_stream=False)}[mode])
+    tun = dataclasses.replace(ops.TUNING, **kw)
+    data(name)
+    main = torch.cuda.current_stream()
+    log, real_call, real_backward = [], ops.call, torch.autograd.backward
+
+    def call(entry, *args):
+        on_main = torch.cuda.current_stream().stream_id == main.stream_id
+        log.append((entry, args[ROWS_ARG[entry]] if _is_stage(entry, args, case.T) else None, on_main))
+        return real_call(entry, *args)
+
+    def backward(*a, **k):
+        log.append(("backward", None, True))
+        return real_backward(*a, **k)
+    monkeypatch.setattr(ops, "call", call)
+    monkeypatch.setattr(torch.autograd, "backward", backward)
+    r = run(ops, name, tun)
+    assert torch.cuda.current_stream().stream_id == main.stream_id
+    check_trace(case, tun, r)
+    if which == "B_first_kept":
+        assert [t["kept"] for t in r.trace[:len(case.chunks)]] == [True] + [False] * (len(case.chunks) - 1)
+    _check_issue_order(case, tun, mode, r.trace, log)
