@@ -44,255 +44,35 @@ __device__ __forceinline__ int tile_of(float x, float y, int tile_shift) {
 }
 
 // ---------------------------------------------------------------------------------------------- binning
-// K1: per-block histogram over a contiguous pixel range -> blockhist[tile][block]
-// (NT = threads of the calling workgroup: the binning kernels' own 1024, or the 512 of the pixel-stage forward when the count of
-// the NEXT batch rides on its launch — the pixel -> block partition depends on per_block only, not on the thread count)
-template <int NT = kBinThreads>
-__device__ __forceinline__ void bin_count_body(int blk, const float2* __restrict__ xy, int64_t P, int64_t per_block, int tile_shift,
-                                               int NB, int32_t* __restrict__ blockhist, int* hist, int32_t* __restrict__ tot_atomic = nullptr) {
-  const int ntiles = 1 << (2 * tile_shift);
-  for (int i = threadIdx.x; i < ntiles; i += NT) hist[i] = 0;
-  __syncthreads();
-  const int64_t lo = (int64_t)blk * per_block;
-  const int64_t hi = lo + per_block < P ? lo + per_block : P;
-  // kBinU pixels per thread and trip, loads issued together: one pixel per trip made the block's time the SUM of eight memory
-  // round trips (one workgroup per CU: there is nobody else to hide them)
-  for (int64_t p0 = lo + threadIdx.x; p0 < hi; p0 += (int64_t)kBinU * NT) {
-    float2 c[kBinU];
-#pragma unroll
-    for (int u = 0; u < kBinU; ++u) { const int64_t p = p0 + (int64_t)u * NT; c[u] = xy[p < hi ? p : hi - 1]; }
-#pragma unroll
-    for (int u = 0; u < kBinU; ++u)
-      if (p0 + (int64_t)u * NT < hi) atomicAdd(&hist[tile_of(c[u].x, c[u].y, tile_shift)], 1);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < ntiles; i += NT) {
-    const int c = hist[i];
-    blockhist[(int64_t)i * NB + blk] = c;
-    if (tot_atomic && c) atomicAdd(tot_atomic + i, c);      // two-launch binning: the tile totals meet in global atomics (bin_scatter2_kernel)
-  }
-}
-
-__global__ void __launch_bounds__(kBinThreads)
-bin_count_kernel(const float2* __restrict__ xy, int64_t P, int64_t per_block, int tile_shift, int NB,
-                 int32_t* __restrict__ blockhist) {
-  extern __shared__ int hist[];
-  bin_count_body((int)blockIdx.x, xy, P, per_block, tile_shift, NB, blockhist, hist);
-}
-
-// K2a: one WAVE per tile row of blockhist [tile][NB] (NB <= 512: 8 consecutive entries per lane): exclusive scan inside the
-// row, row total to tot[tile].  grid = ceil(ntiles / 4) blocks of 4 waves.
-constexpr int kBinMaxBlocks = 512;
-__global__ void __launch_bounds__(256)
-bin_rowscan_kernel(int32_t* __restrict__ blockhist, int NB, int ntiles, int32_t* __restrict__ tot) {
-  const int lane = threadIdx.x & 63;
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= ntiles) return;
-  int32_t* row = blockhist + (int64_t)t * NB;
-  int v[8], mine = 0;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) { const int b = 8 * lane + q; v[q] = b < NB ? row[b] : 0; mine += v[q]; }
-  int incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-  int ex = incl - mine;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) { const int b = 8 * lane + q; if (b < NB) row[b] = ex; ex += v[q]; }
-  if (lane == 63) tot[t] = incl;
-}
-
-// K2b (one block): exclusive scan over tiles of (pixels, items); tile_off, tile_item_base, work-item table.
-__global__ void __launch_bounds__(kBinThreads)
-bin_scan_kernel(const int32_t* __restrict__ tot, int tile_shift, int chunk, int32_t* __restrict__ tile_off,
-                int32_t* __restrict__ tile_item_base, int4* __restrict__ items, int32_t* __restrict__ n_items) {
-  __shared__ int wsum[kBinThreads / 64], wsum2[kBinThreads / 64];
-  const int ntiles = 1 << (2 * tile_shift);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int per = (ntiles + kBinThreads - 1) / kBinThreads;      // consecutive tiles per thread
-  int mytot = 0, myit = 0;
-  for (int q = 0; q < per; ++q) {
-    const int t = tid * per + q;
-    if (t < ntiles) { const int c = tot[t]; mytot += c; myit += (c + chunk - 1) / chunk; }
-  }
-  int a = mytot, n2 = myit;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int ua = __shfl_up(a, o, 64), un = __shfl_up(n2, o, 64);
-    if (lane >= o) { a += ua; n2 += un; }
-  }
-  if (lane == 63) { wsum[wave] = a; wsum2[wave] = n2; }
-  __syncthreads();
-  int off = a - mytot, ioff = n2 - myit;
-  for (int w = 0; w < wave; ++w) { off += wsum[w]; ioff += wsum2[w]; }
-  for (int q = 0; q < per; ++q) {
-    const int t = tid * per + q;
-    if (t < ntiles) {
-      const int total = tot[t];
-      const int nit = (total + chunk - 1) / chunk;
-      tile_off[t] = off;
-      tile_item_base[t] = ioff;
-      for (int jj = 0; jj < nit; ++jj) {
-        const int cnt = (total - jj * chunk) < chunk ? (total - jj * chunk) : chunk;
-        items[ioff + jj] = make_int4(off + jj * chunk, cnt, t, nit);
-      }
-      off += total;
-      ioff += nit;
-    }
-  }
-  if (tid == kBinThreads - 1) {
-    tile_off[ntiles] = off; tile_item_base[ntiles] = ioff;
-    n_items[0] = ioff;
-    n_items[1] = n_items[2] = n_items[3] = 0;     // work / exit counters of the persistent interleaved kernels (il_claim, il_done)
-  }
-}
-
-// K3: scatter (x, y, original index) into tile order.  Same pixel->block partition as K1.
-__device__ __forceinline__ void bin_scatter_body(int blk, const float2* __restrict__ xy, int64_t P, int64_t per_block, int tile_shift,
-                                                 int NB, const int32_t* __restrict__ blockhist, const int32_t* __restrict__ tile_off,
-                                                 float4* __restrict__ sorted, int* cursor) {
-  const int ntiles = 1 << (2 * tile_shift);
-  for (int i = threadIdx.x; i < ntiles; i += kBinThreads) cursor[i] = tile_off[i] + blockhist[(int64_t)i * NB + blk];
-  __syncthreads();
-  const int64_t lo = (int64_t)blk * per_block;
-  const int64_t hi = lo + per_block < P ? lo + per_block : P;
-  for (int64_t p0 = lo + threadIdx.x; p0 < hi; p0 += (int64_t)kBinU * kBinThreads) {
-    float2 c[kBinU];
-    int pos[kBinU];
-#pragma unroll
-    for (int u = 0; u < kBinU; ++u) { const int64_t p = p0 + (int64_t)u * kBinThreads; c[u] = xy[p < hi ? p : hi - 1]; }
-#pragma unroll
-    for (int u = 0; u < kBinU; ++u)
-      pos[u] = (p0 + (int64_t)u * kBinThreads < hi) ? atomicAdd(&cursor[tile_of(c[u].x, c[u].y, tile_shift)], 1) : -1;
-#pragma unroll
-    for (int u = 0; u < kBinU; ++u)
-      if (pos[u] >= 0) sorted[pos[u]] = make_float4(c[u].x, c[u].y, __int_as_float((int)(p0 + (int64_t)u * kBinThreads)), 0.f);
-  }
-}
-
-__global__ void __launch_bounds__(kBinThreads)
-bin_scatter_kernel(const float2* __restrict__ xy, int64_t P, int64_t per_block, int tile_shift, int NB,
-                   const int32_t* __restrict__ blockhist, const int32_t* __restrict__ tile_off, float4* __restrict__ sorted) {
-  extern __shared__ int cursor[];
-  bin_scatter_body((int)blockIdx.x, xy, P, per_block, tile_shift, NB, blockhist, tile_off, sorted, cursor);
-}
-
-// TWO-LAUNCH BINNING (count -> scatter): the row scan and the tile scan — two launches of ~5 us each inside a replayed step, all
-// of it launch latency — fold into the scatter launch.  The count blocks add their histograms to per-tile totals with global
-// atomics (`pws`: a PERSISTENT zero-initialised workspace [totals ntiles | cursors ntiles | ticket]); every scatter block
-// scans the totals itself (1024 tiles: one per thread), reserves its pixels' places in each tile with one atomic on the tile's
-// cursor (the order of the blocks inside a tile is whatever the atomics make it — as the order of pixels inside a block
-// already is), block 0 also writes the tables the pixel stage reads, and the LAST block out (ticket) puts the workspace back to
-// zero for the next call.  No block ever waits for another block.
-// `cursor` [ntiles], `wsum` / `wsum2` [kBinThreads / 64] and `s_last` live in the caller's LDS (the kernel below, or the tail of the
-// pixel-stage backward when the scatter of the NEXT batch rides there as claimed tasks: tiled_bwd_il_kernel).  pws = [totals
-// ntiles | cursors ntiles | ticket | task-claim counter of the riding form].
-__device__ __forceinline__ void bin_scatter2_body(const int blk, const float2* __restrict__ xy, int64_t P, int64_t per_block, int tile_shift,
-                                                  int NB, int chunk, const int32_t* __restrict__ blockhist, int32_t* __restrict__ pws,
-                                                  int32_t* __restrict__ tile_off, int32_t* __restrict__ tile_item_base,
-                                                  int4* __restrict__ items, int32_t* __restrict__ n_items, float4* __restrict__ sorted,
-                                                  int* cursor, int* wsum, int* wsum2, int* s_last) {
-  const int ntiles = 1 << (2 * tile_shift);
-  int32_t* tot = pws;
-  int32_t* gcur = pws + ntiles;
-  int32_t* ticket = pws + 2 * ntiles;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int per = (ntiles + kBinThreads - 1) / kBinThreads;      // consecutive tiles per thread
-  // exclusive scans over tiles of (pixels, items), as bin_scan_kernel
-  int mytot = 0, myit = 0;
-  for (int q = 0; q < per; ++q) {
-    const int t = tid * per + q;
-    if (t < ntiles) { const int c = tot[t]; mytot += c; myit += (c + chunk - 1) / chunk; }
-  }
-  int a = mytot, n2 = myit;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int ua = __shfl_up(a, o, 64), un = __shfl_up(n2, o, 64);
-    if (lane >= o) { a += ua; n2 += un; }
-  }
-  if (lane == 63) { wsum[wave] = a; wsum2[wave] = n2; }
-  __syncthreads();
-  int off = a - mytot, ioff = n2 - myit;
-  for (int w = 0; w < wave; ++w) { off += wsum[w]; ioff += wsum2[w]; }
-  for (int q = 0; q < per; ++q) {
-    const int t = tid * per + q;
-    if (t < ntiles) {
-      const int total = tot[t];
-      const int nit = (total + chunk - 1) / chunk;
-      // this block's first place in tile t: behind the blocks that reserved before it
-      const int mine = blockhist[(int64_t)t * NB + blk];
-      cursor[t] = off + (mine ? atomicAdd(gcur + t, mine) : 0);
-      if (blk == 0) {
-        tile_off[t] = off;
-        tile_item_base[t] = ioff;
-        for (int jj = 0; jj < nit; ++jj) {
-          const int cnt = (total - jj * chunk) < chunk ? (total - jj * chunk) : chunk;
-          items[ioff + jj] = make_int4(off + jj * chunk, cnt, t, nit);
-        }
-      }
-      off += total;
-      ioff += nit;
-    }
-  }
-  if (blk == 0 && tid == kBinThreads - 1) {
-    tile_off[ntiles] = off; tile_item_base[ntiles] = ioff;
-    n_items[0] = ioff;
-    n_items[1] = n_items[2] = n_items[3] = 0;
-  }
-  __syncthreads();
-  const int64_t lo = (int64_t)blk * per_block;
-  const int64_t hi = lo + per_block < P ? lo + per_block : P;
-  for (int64_t p0 = lo + tid; p0 < hi; p0 += (int64_t)kBinU * kBinThreads) {     // (loads together: see bin_count_body)
-    float2 c[kBinU];
-    int pos[kBinU];
-#pragma unroll
-    for (int u = 0; u < kBinU; ++u) { const int64_t p = p0 + (int64_t)u * kBinThreads; c[u] = xy[p < hi ? p : hi - 1]; }
-#pragma unroll
-    for (int u = 0; u < kBinU; ++u)
-      pos[u] = (p0 + (int64_t)u * kBinThreads < hi) ? atomicAdd(&cursor[tile_of(c[u].x, c[u].y, tile_shift)], 1) : -1;
-#pragma unroll
-    for (int u = 0; u < kBinU; ++u)
-      if (pos[u] >= 0) sorted[pos[u]] = make_float4(c[u].x, c[u].y, __int_as_float((int)(p0 + (int64_t)u * kBinThreads)), 0.f);
-  }
-  // last block out clears the workspace (every block has finished reading the totals and reserving on the cursors by then)
-  __syncthreads();
-  if (tid == 0) *s_last = atomicAdd(ticket, 1) == NB - 1;
-  __syncthreads();
-  if (*s_last) {
-    for (int t = tid; t < ntiles; t += kBinThreads) { tot[t] = 0; gcur[t] = 0; }
-    if (tid == 0) *ticket = 0;
-  }
-}
-
-__global__ void __launch_bounds__(kBinThreads)
-bin_scatter2_kernel(const float2* __restrict__ xy, int64_t P, int64_t per_block, int tile_shift, int NB, int chunk,
-                    const int32_t* __restrict__ blockhist, int32_t* __restrict__ pws, int32_t* __restrict__ tile_off,
-                    int32_t* __restrict__ tile_item_base, int4* __restrict__ items, int32_t* __restrict__ n_items,
-                    float4* __restrict__ sorted) {
-  extern __shared__ int cursor[];                 // [ntiles]
-  __shared__ int wsum[kBinThreads / 64], wsum2[kBinThreads / 64];
-  __shared__ int s_last;
-  bin_scatter2_body((int)blockIdx.x, xy, P, per_block, tile_shift, NB, chunk, blockhist, pws, tile_off, tile_item_base, items, n_items,
-                    sorted, cursor, wsum, wsum2, &s_last);
-}
-
-// RESERVING COUNT -> SCATTER (round 4, late): the form gngf_bin_pixels2 and the riders use.  A scatter task of the form above
-// spends a third of its ~14 us on work every task repeats — the scan over the tile totals, one global atomic per non-empty tile
-// to reserve its places — and as a task in the tail of the pixel-stage backward it has to fit a hole of one work item (22 us): one
-// fits, two do not.  Here the COUNT side does that work once: a count block reserves its places in every tile as soon as it
-// knows its histogram (one RETURNING atomic per non-empty tile on the tile's cursor — the cursors end up holding the tile
-// totals) and keeps the offsets, block-major, for the scatter block of the same index; the LAST count block out (ticket: its
-// own atomics have returned before it takes one, so every reservation is performed) scans the totals — read with device-scope
-// atomic loads: they were only ever touched by atomics — and writes the tile tables and the work items.  A scatter block then
-// reads two coalesced rows (tile offsets + its own offsets) and moves its pixels: no scan, no global atomics at all.
-// Nobody puts the cursors back to zero either (that took a "last scatter block out" ticket: a returning atomic and two barriers per
-// task): they RUN ON from job to job, and the last count block out notes where this job's successor starts (`start`); offsets and
-// totals are differences in unsigned arithmetic, correct through any wrap-around.
-// pws = [cursors ntiles | start ntiles | (unused) | task counter | count ticket]: zero before its first use, never reset.
+// A counting sort of the batch's pixels by spatial tile.  Three forms are reachable; they differ in how many launches they take
+// and in where a tile's total and a block's first place in a tile come from, and are built from ONE set of stages (below):
+//   four-launch           bin_count[_ride/_vride] > bin_rowscan > bin_scan > bin_scatter[_ride]
+//                         (gngf_bin_pixels; gngf_encode_tiled_prepare with a zero-fill or without persistent counters)
+//   two-launch "prepare"  bin_count_vride > bin_scatter2: the rows are not scanned — the count blocks add their histograms to
+//                         per-tile totals with global atomics, every scatter block scans the totals itself and reserves its places
+//                         in each tile with one atomic on the tile's cursor; the last scatter block out puts the counters back to zero
+//                         (gngf_encode_tiled_prepare with persistent counters and no zero-fill)
+//   reserving             bin_count_reserve > bin_scatter3, or as riders of the pixel-stage launches: a count block reserves its
+//                         places as soon as it knows its histogram, the LAST count block out writes the tables, a scatter block
+//                         reads two coalesced rows and moves its pixels; the cursors run on from job to job and are never reset
+//                         (gngf_bin_pixels2; gngf_encode_tiled_fwd_fused(next_count) + gngf_encode_tiled_bwd(next_bin))
+// No block ever waits for another block in any of them.
+//
+// One job, as every binning kernel and rider takes it (by value).  The caller's two scratch buffers mean different things by form:
+//   blockhist  four-launch and "prepare": [tile][NB] — the count blocks' histograms (four-launch: turned into exclusive prefixes
+//              along each row by bin_rowscan) — and `ntiles` row totals behind them (four-launch only: bin_tot)
+//              reserving: [NB][ntiles] — first place of block b in tile t, relative to the tile's start
+//   pws        four-launch: NULL
+//              "prepare":  [totals ntiles | cursors ntiles | ticket of the scatter blocks], zero between calls
+//              reserving:  [cursors ntiles | start ntiles | (unused) | task counter of the riding scatter | ticket of the count
+//                          blocks]: zero before its first use, never reset.  `start` = the cursors' values when the current job
+//                          began, noted by its predecessor's last count block; offsets and totals are differences in unsigned
+//                          arithmetic, correct through any wrap-around.
 struct BinJobDev {
   const float2* xy;
-  int64_t P, per_block;
-  int NB, tile_shift, chunk;
-  int32_t* blockbase;            // [NB][ntiles]: first place of block b in tile t, relative to the tile's start
+  int64_t P, per_block;          // per_block: pixels [blk * per_block, (blk + 1) * per_block) belong to binning block blk
+  int NB, tile_shift, chunk;     // NB = 0: no job (the riders)
+  int32_t* blockhist;
   int32_t* pws;
   int32_t *tile_off, *tile_item_base;
   int4* items;
@@ -300,21 +80,23 @@ struct BinJobDev {
   float4* sorted;
 };
 
+constexpr int kBinMaxBlocks = 512;
+
+__device__ __forceinline__ int32_t* bin_tot(const BinJobDev& j) { return j.blockhist + ((int64_t)j.NB << (2 * j.tile_shift)); }
+
+// STAGE 1, histogram: hist[tile] (LDS) = pixels of block `blk` in the tile; ends on a barrier.
+// (NT = threads of the calling workgroup: the binning kernels' own 1024, or the 512 of the pixel-stage forward when the count of
+// the NEXT batch rides on its launch — the pixel -> block partition depends on per_block only, not on the thread count)
 template <int NT>
-__device__ __forceinline__ void bin_count_reserve_body(const int blk, const BinJobDev& j, int* hist /* LDS: ntiles + 2 NT/64 + 1 ints */) {
+__device__ __forceinline__ void bin_histogram(const int blk, const BinJobDev& j, int* hist) {
   const int ntiles = 1 << (2 * j.tile_shift);
-  int* wsum = hist + ntiles;
-  int* wsum2 = wsum + NT / 64;
-  int* s_last = wsum2 + NT / 64;
-  unsigned* gcur = reinterpret_cast<unsigned*>(j.pws);
-  unsigned* start = gcur + ntiles;                            // the cursors' values when this job began (written by its predecessor)
-  int32_t* tcount = j.pws + 2 * ntiles + 2;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int i = tid; i < ntiles; i += NT) hist[i] = 0;
+  for (int i = threadIdx.x; i < ntiles; i += NT) hist[i] = 0;
   __syncthreads();
   const int64_t lo = (int64_t)blk * j.per_block;
   const int64_t hi = lo + j.per_block < j.P ? lo + j.per_block : j.P;
-  for (int64_t p0 = lo + tid; p0 < hi; p0 += (int64_t)kBinU * NT) {              // (loads together: see bin_count_body)
+  // kBinU pixels per thread and trip, loads issued together: one pixel per trip made the block's time the SUM of eight memory
+  // round trips (one workgroup per CU: there is nobody else to hide them)
+  for (int64_t p0 = lo + threadIdx.x; p0 < hi; p0 += (int64_t)kBinU * NT) {
     float2 c[kBinU];
 #pragma unroll
     for (int u = 0; u < kBinU; ++u) { const int64_t p = p0 + (int64_t)u * NT; c[u] = j.xy[p < hi ? p : hi - 1]; }
@@ -323,27 +105,21 @@ __device__ __forceinline__ void bin_count_reserve_body(const int blk, const BinJ
       if (p0 + (int64_t)u * NT < hi) atomicAdd(&hist[tile_of(c[u].x, c[u].y, j.tile_shift)], 1);
   }
   __syncthreads();
-  int32_t* mybase = j.blockbase + (int64_t)blk * ntiles;
-  for (int i = tid; i < ntiles; i += NT) {
-    const int c = hist[i];
-    mybase[i] = c ? (int)(atomicAdd(gcur + i, (unsigned)c) - start[i]) : 0;      // the store needs the atomic's return: it has been performed by then
-  }
-  __syncthreads();
-  if (tid == 0) *s_last = atomicAdd(tcount, 1) == j.NB - 1;
-  __syncthreads();
-  if (!*s_last) return;
-  // last count block out: cursors = tile totals.  Exclusive scans over tiles of (pixels, items), as bin_scan_kernel.
+}
+
+// STAGE 2, tile tables (one workgroup of NT threads): exclusive scan over tiles of (pixels, items) -> tile_off, tile_item_base,
+// the work items, the closing entries and n_items.  total_of(t) = pixels in tile t (asked twice per tile); per_tile(t, off) runs
+// once per tile with the tile's first place; only a workgroup with `write` set stores the tables.  wsum: 2 * NT / 64 ints of LDS.
+template <int NT, typename Total, typename PerTile>
+__device__ __forceinline__ void bin_tile_tables(const BinJobDev& j, const bool write, int* wsum, Total total_of, PerTile per_tile) {
+  const int ntiles = 1 << (2 * j.tile_shift);
+  int* wsum2 = wsum + NT / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int per = (ntiles + NT - 1) / NT;                   // consecutive tiles per thread
   int mytot = 0, myit = 0;
   for (int q = 0; q < per; ++q) {
     const int t = tid * per + q;
-    if (t < ntiles) {
-      const unsigned now = __hip_atomic_load(gcur + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int c = (int)(now - start[t]);
-      start[t] = now;                                        // where the NEXT job's reservations begin (every block of this one is done)
-      hist[t] = c;                                           // (the histogram is no longer needed: keep the totals there)
-      mytot += c; myit += (c + j.chunk - 1) / j.chunk;
-    }
+    if (t < ntiles) { const int c = total_of(t); mytot += c; myit += (c + j.chunk - 1) / j.chunk; }
   }
   int a = mytot, n2 = myit;
 #pragma unroll
@@ -358,36 +134,34 @@ __device__ __forceinline__ void bin_count_reserve_body(const int blk, const BinJ
   for (int q = 0; q < per; ++q) {
     const int t = tid * per + q;
     if (t < ntiles) {
-      const int total = hist[t];
+      const int total = total_of(t);
       const int nit = (total + j.chunk - 1) / j.chunk;
-      j.tile_off[t] = off;
-      j.tile_item_base[t] = ioff;
-      for (int jj = 0; jj < nit; ++jj) {
-        const int cnt = (total - jj * j.chunk) < j.chunk ? (total - jj * j.chunk) : j.chunk;
-        j.items[ioff + jj] = make_int4(off + jj * j.chunk, cnt, t, nit);
+      per_tile(t, off);
+      if (write) {
+        j.tile_off[t] = off;
+        j.tile_item_base[t] = ioff;
+        for (int jj = 0; jj < nit; ++jj) {
+          const int cnt = (total - jj * j.chunk) < j.chunk ? (total - jj * j.chunk) : j.chunk;
+          j.items[ioff + jj] = make_int4(off + jj * j.chunk, cnt, t, nit);
+        }
       }
       off += total;
       ioff += nit;
     }
   }
-  if (tid == NT - 1) {
+  if (write && tid == NT - 1) {
     j.tile_off[ntiles] = off; j.tile_item_base[ntiles] = ioff;
     j.n_items[0] = ioff;
-    j.n_items[1] = j.n_items[2] = j.n_items[3] = 0;
-    *tcount = 0;                                             // (read again by atomics of a LATER launch only)
+    j.n_items[1] = j.n_items[2] = j.n_items[3] = 0;     // work / exit counters of the persistent interleaved kernels (il_claim, il_done)
   }
 }
 
-// scatter block `blk` (1024 threads): cursor [ntiles] in the caller's LDS
-__device__ __forceinline__ void bin_scatter3_body(const int blk, const BinJobDev& j, int* cursor) {
-  const int ntiles = 1 << (2 * j.tile_shift);
-  const int tid = threadIdx.x;
-  const int32_t* mybase = j.blockbase + (int64_t)blk * ntiles;
-  for (int t = tid; t < ntiles; t += kBinThreads) cursor[t] = j.tile_off[t] + mybase[t];
-  __syncthreads();
+// STAGE 3, move pixels (a workgroup of kBinThreads): (x, y, bits(original index), 0) of block `blk`'s pixels into tile order.
+// cursor[tile] (LDS) = the block's first place in the tile, set by the form and visible (barrier) on entry.
+__device__ __forceinline__ void bin_move_pixels(const int blk, const BinJobDev& j, int* cursor) {
   const int64_t lo = (int64_t)blk * j.per_block;
   const int64_t hi = lo + j.per_block < j.P ? lo + j.per_block : j.P;
-  for (int64_t p0 = lo + tid; p0 < hi; p0 += (int64_t)kBinU * kBinThreads) {
+  for (int64_t p0 = lo + threadIdx.x; p0 < hi; p0 += (int64_t)kBinU * kBinThreads) {     // (loads together: see bin_histogram)
     float2 c[kBinU];
     int pos[kBinU];
 #pragma unroll
@@ -401,46 +175,178 @@ __device__ __forceinline__ void bin_scatter3_body(const int blk, const BinJobDev
   }
 }
 
-// the two as launches of their own (gngf_bin_pixels2: the first step of a replay, eager steps); workgroups [NB, NB + zblocks)
-// of the count launch clear `zero` (as bin_count_ride_kernel)
-__global__ void __launch_bounds__(kBinThreads)
-bin_count_reserve_kernel(const BinJobDev j, float4* __restrict__ zero, int64_t nvec, int zblocks) {
-  extern __shared__ int hist[];
-  if ((int)blockIdx.x < j.NB) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) j.pws[2 * (1 << (2 * j.tile_shift)) + 1] = 0;      // the riding form's task counter
-    bin_count_reserve_body<kBinThreads>((int)blockIdx.x, j, hist);
-    return;
-  }
-  const int64_t zb = (int)blockIdx.x - j.NB;
+// STAGE 4, zero-fill rider: block `zb` of `zblocks` clears its share of `zero` (nvec float4) — the gradient buffer the backward
+// pass will accumulate into (64 MiB at T = 2^19).  A count keeps 128 of the 256 CUs busy for ~8 us; the fill runs on the
+// others, instead of being a launch (or a stream) of its own.
+__device__ __forceinline__ void bin_zero_fill_block(const int zb, float4* __restrict__ zero, int64_t nvec, int zblocks) {
   const int64_t per = (nvec + zblocks - 1) / zblocks;
   const int64_t lo = zb * per, hi = lo + per < nvec ? lo + per : nvec;
   const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int64_t e = lo + threadIdx.x; e < hi; e += kBinThreads) zero[e] = z;
+}
+
+// ---- four-launch form (and the count of the "prepare" form, which differs in one line)
+// K1: the block's histogram -> column `blk` of blockhist [tile][NB]; with persistent counters ("prepare") the tile totals meet
+// in global atomics as well (bin_scatter2_kernel)
+__device__ __forceinline__ void bin_count_block(const int blk, const BinJobDev& j, int* hist) {
+  bin_histogram<kBinThreads>(blk, j, hist);
+  const int ntiles = 1 << (2 * j.tile_shift);
+  for (int i = threadIdx.x; i < ntiles; i += kBinThreads) {
+    const int c = hist[i];
+    j.blockhist[(int64_t)i * j.NB + blk] = c;
+    if (j.pws && c) atomicAdd(j.pws + i, c);
+  }
+}
+
+__global__ void __launch_bounds__(kBinThreads)
+bin_count_kernel(const BinJobDev j) {
+  extern __shared__ int hist[];
+  bin_count_block((int)blockIdx.x, j, hist);
+}
+
+// K1 with the zero-fill riding on the launch: workgroups [NB, NB + zblocks)
+__global__ void __launch_bounds__(kBinThreads)
+bin_count_ride_kernel(const BinJobDev j, float4* __restrict__ zero, int64_t nvec, int zblocks) {
+  extern __shared__ int hist[];
+  if ((int)blockIdx.x < j.NB) bin_count_block((int)blockIdx.x, j, hist);
+  else bin_zero_fill_block((int)blockIdx.x - j.NB, zero, nvec, zblocks);
+}
+
+// K2a: one WAVE per tile row of blockhist [tile][NB] (NB <= 512: 8 consecutive entries per lane): exclusive scan inside the
+// row, row total to tot[tile].  grid = ceil(ntiles / 4) blocks of 4 waves.
+__global__ void __launch_bounds__(256)
+bin_rowscan_kernel(const BinJobDev j) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= (1 << (2 * j.tile_shift))) return;
+  const int NB = j.NB;
+  int32_t* row = j.blockhist + (int64_t)t * NB;
+  int v[8], mine = 0;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) { const int b = 8 * lane + q; v[q] = b < NB ? row[b] : 0; mine += v[q]; }
+  int incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
+  int ex = incl - mine;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) { const int b = 8 * lane + q; if (b < NB) row[b] = ex; ex += v[q]; }
+  if (lane == 63) bin_tot(j)[t] = incl;
+}
+
+// K2b (one block): the tile tables from the row totals
+__global__ void __launch_bounds__(kBinThreads)
+bin_scan_kernel(const BinJobDev j) {
+  __shared__ int wsum[2 * (kBinThreads / 64)];
+  const int32_t* tot = bin_tot(j);
+  bin_tile_tables<kBinThreads>(j, true, wsum, [&](int t) { return tot[t]; }, [](int, int) {});
+}
+
+// K3: the block's first place in a tile = the tile's start + the scanned row entry.  Same pixel -> block partition as K1.
+__device__ __forceinline__ void bin_scatter_block(const int blk, const BinJobDev& j, int* cursor) {
+  const int ntiles = 1 << (2 * j.tile_shift);
+  for (int i = threadIdx.x; i < ntiles; i += kBinThreads) cursor[i] = j.tile_off[i] + j.blockhist[(int64_t)i * j.NB + blk];
+  __syncthreads();
+  bin_move_pixels(blk, j, cursor);
+}
+
+__global__ void __launch_bounds__(kBinThreads)
+bin_scatter_kernel(const BinJobDev j) {
+  extern __shared__ int cursor[];
+  bin_scatter_block((int)blockIdx.x, j, cursor);
+}
+
+// ---- two-launch "prepare" form: the row scan and the tile scan — two launches of ~5 us each inside a replayed step, all of it
+// launch latency — fold into the scatter launch.  Every block scans the totals itself (1024 tiles: one per thread) and takes its
+// places in each tile behind the blocks that reserved before it (the order of the blocks inside a tile is whatever the atomics
+// make it — as the order of pixels inside a block already is); block 0 also writes the tables the pixel stage reads.
+__global__ void __launch_bounds__(kBinThreads)
+bin_scatter2_kernel(const BinJobDev j) {
+  extern __shared__ int cursor[];                 // [ntiles]
+  __shared__ int wsum[2 * (kBinThreads / 64)];
+  __shared__ int s_last;
+  const int blk = (int)blockIdx.x, tid = threadIdx.x;
+  const int ntiles = 1 << (2 * j.tile_shift);
+  int32_t* tot = j.pws;
+  int32_t* gcur = j.pws + ntiles;
+  int32_t* ticket = j.pws + 2 * ntiles;
+  bin_tile_tables<kBinThreads>(j, blk == 0, wsum, [&](int t) { return tot[t]; }, [&](int t, int off) {
+    const int mine = j.blockhist[(int64_t)t * j.NB + blk];
+    cursor[t] = off + (mine ? atomicAdd(gcur + t, mine) : 0);
+  });
+  __syncthreads();
+  bin_move_pixels(blk, j, cursor);
+  // last block out clears the counters (every block has finished reading the totals and reserving on the cursors by then)
+  __syncthreads();
+  if (tid == 0) s_last = atomicAdd(ticket, 1) == j.NB - 1;
+  __syncthreads();
+  if (s_last) {
+    for (int t = tid; t < ntiles; t += kBinThreads) { tot[t] = 0; gcur[t] = 0; }
+    if (tid == 0) *ticket = 0;
+  }
+}
+
+// ---- reserving form.  A scatter block of the form above spends a third of its ~14 us on work every block repeats — the scan
+// over the tile totals, one global atomic per non-empty tile — and as a task in the tail of the pixel-stage backward it has to
+// fit a hole of one work item (22 us): one fits, two do not.  Here the COUNT side does that work once: a count block reserves its
+// places in every tile as soon as it knows its histogram (one RETURNING atomic per non-empty tile on the tile's cursor — the
+// cursors end up holding the tile totals) and keeps the offsets, block-major, for the scatter block of the same index; the LAST
+// count block out (ticket: its own atomics have returned before it takes one, so every reservation is performed) reads the
+// totals — with device-scope atomic loads: they were only ever touched by atomics — and writes the tables.  A scatter block
+// has no scan and no global atomics at all.  Nobody puts the cursors back to zero either (that took a "last scatter block out"
+// ticket: a returning atomic and two barriers per task): they run on, see `pws` at BinJobDev.
+// Count block `blk` (NT threads: a kernel of its own, or a rider of tiled_fwd_il_kernel).  hist: ntiles + 2 NT/64 + 1 ints of LDS.
+template <int NT>
+__device__ __forceinline__ void bin_count_reserve_block(const int blk, const BinJobDev& j, int* hist) {
+  const int ntiles = 1 << (2 * j.tile_shift);
+  int* wsum = hist + ntiles;
+  int* s_last = wsum + 2 * (NT / 64);
+  unsigned* gcur = reinterpret_cast<unsigned*>(j.pws);
+  unsigned* start = gcur + ntiles;
+  int32_t* tcount = j.pws + 2 * ntiles + 2;
+  const int tid = threadIdx.x;
+  if (blk == 0 && tid == 0) j.pws[2 * ntiles + 1] = 0;        // the task counter of the riding scatter (tiled_bwd_il_kernel)
+  bin_histogram<NT>(blk, j, hist);
+  int32_t* mybase = j.blockhist + (int64_t)blk * ntiles;
+  for (int i = tid; i < ntiles; i += NT) {
+    const int c = hist[i];
+    mybase[i] = c ? (int)(atomicAdd(gcur + i, (unsigned)c) - start[i]) : 0;      // the store needs the atomic's return: it has been performed by then
+  }
+  __syncthreads();
+  if (tid == 0) *s_last = atomicAdd(tcount, 1) == j.NB - 1;
+  __syncthreads();
+  if (!*s_last) return;
+  // last count block out: the tile totals, parked where the histogram was, and where the NEXT job's reservations begin
+  for (int t = tid; t < ntiles; t += NT) {
+    const unsigned now = __hip_atomic_load(gcur + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    hist[t] = (int)(now - start[t]);
+    start[t] = now;
+  }
+  __syncthreads();
+  bin_tile_tables<NT>(j, true, wsum, [&](int t) { return hist[t]; }, [](int, int) {});
+  if (tid == 0) *tcount = 0;                                   // (read again by atomics of a LATER launch only)
+}
+
+// Scatter block `blk` (kBinThreads: a kernel of its own, or a task in the tail of tiled_bwd_il_kernel): cursor [ntiles] of LDS
+__device__ __forceinline__ void bin_scatter3_block(const int blk, const BinJobDev& j, int* cursor) {
+  const int ntiles = 1 << (2 * j.tile_shift);
+  const int32_t* mybase = j.blockhist + (int64_t)blk * ntiles;
+  for (int t = threadIdx.x; t < ntiles; t += kBinThreads) cursor[t] = j.tile_off[t] + mybase[t];
+  __syncthreads();
+  bin_move_pixels(blk, j, cursor);
+}
+
+// the two as launches of their own (gngf_bin_pixels2: the first step of a replay, eager steps), the zero-fill riding on the count
+__global__ void __launch_bounds__(kBinThreads)
+bin_count_reserve_kernel(const BinJobDev j, float4* __restrict__ zero, int64_t nvec, int zblocks) {
+  extern __shared__ int hist[];
+  if ((int)blockIdx.x < j.NB) bin_count_reserve_block<kBinThreads>((int)blockIdx.x, j, hist);
+  else bin_zero_fill_block((int)blockIdx.x - j.NB, zero, nvec, zblocks);
 }
 
 __global__ void __launch_bounds__(kBinThreads)
 bin_scatter3_kernel(const BinJobDev j) {
   extern __shared__ int cursor[];                 // [ntiles]
-  bin_scatter3_body((int)blockIdx.x, j, cursor);
-}
-
-// K1 with a ZERO-FILL riding on the launch: workgroups [NB, NB + zblocks) clear `zero` (nvec float4) instead — the gradient
-// buffer the backward pass will accumulate into (64 MiB at T = 2^19).  The count keeps 128 of the 256 CUs busy for ~8 us;
-// the fill runs on the others, instead of being a launch (or a stream) of its own.
-__global__ void __launch_bounds__(kBinThreads)
-bin_count_ride_kernel(const float2* __restrict__ xy, int64_t P, int64_t per_block, int tile_shift, int NB,
-                      int32_t* __restrict__ blockhist, float4* __restrict__ zero, int64_t nvec, int zblocks,
-                      int32_t* __restrict__ tot_atomic = nullptr) {
-  extern __shared__ int hist[];
-  if ((int)blockIdx.x < NB) {
-    bin_count_body((int)blockIdx.x, xy, P, per_block, tile_shift, NB, blockhist, hist, tot_atomic);
-    return;
-  }
-  const int64_t zb = (int)blockIdx.x - NB;
-  const int64_t per = (nvec + zblocks - 1) / zblocks;
-  const int64_t lo = zb * per, hi = lo + per < nvec ? lo + per : nvec;
-  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int64_t e = lo + threadIdx.x; e < hi; e += kBinThreads) zero[e] = z;
+  bin_scatter3_block((int)blockIdx.x, j, cursor);
 }
 
 // ---------------------------------------------------------------------------------------------- vertex stage
@@ -536,18 +442,16 @@ __device__ __forceinline__ void vertex_ride_block(int vb, const TT* __restrict__
 // round the scatter launch took 21 us.)
 template <int F, bool VT, typename TT>
 __global__ void __launch_bounds__(kBinThreads)
-bin_scatter_ride_kernel(const float2* __restrict__ xy, int64_t P, int64_t per_block, int tile_shift, int NB,
-                        const int32_t* __restrict__ blockhist, const int32_t* __restrict__ tile_off, float4* __restrict__ sorted,
-                        const TT* __restrict__ tables, const int32_t* __restrict__ vert_idx,
+bin_scatter_ride_kernel(const BinJobDev j, const TT* __restrict__ tables, const int32_t* __restrict__ vert_idx,
                         const float* __restrict__ vert_w, const int32_t* __restrict__ n_ls, float* __restrict__ G,
                         float* __restrict__ dG_zero, int Ls, int64_t T, int K, int vstride, int64_t NV, bool pow2, int64_t vtot,
                         int zero_words, float* __restrict__ clear_rows) {
   extern __shared__ int cursor[];
-  if ((int)blockIdx.x < NB) {
-    bin_scatter_body((int)blockIdx.x, xy, P, per_block, tile_shift, NB, blockhist, tile_off, sorted, cursor);
+  if ((int)blockIdx.x < j.NB) {
+    bin_scatter_block((int)blockIdx.x, j, cursor);
     return;
   }
-  vertex_ride_block<F, VT, TT>((int)blockIdx.x - NB, tables, vert_idx, vert_w, n_ls, G, dG_zero, Ls, T, K, vstride, NV, pow2, vtot, zero_words,
+  vertex_ride_block<F, VT, TT>((int)blockIdx.x - j.NB, tables, vert_idx, vert_w, n_ls, G, dG_zero, Ls, T, K, vstride, NV, pow2, vtot, zero_words,
                                clear_rows);
 }
 
@@ -556,17 +460,16 @@ bin_scatter_ride_kernel(const float2* __restrict__ xy, int64_t P, int64_t per_bl
 // then runs alone.
 template <int F, bool VT, typename TT>
 __global__ void __launch_bounds__(kBinThreads)
-bin_count_vride_kernel(const float2* __restrict__ xy, int64_t P, int64_t per_block, int tile_shift, int NB,
-                       int32_t* __restrict__ blockhist, const TT* __restrict__ tables, const int32_t* __restrict__ vert_idx,
+bin_count_vride_kernel(const BinJobDev j, const TT* __restrict__ tables, const int32_t* __restrict__ vert_idx,
                        const float* __restrict__ vert_w, const int32_t* __restrict__ n_ls, float* __restrict__ G,
                        float* __restrict__ dG_zero, int Ls, int64_t T, int K, int vstride, int64_t NV, bool pow2, int64_t vtot,
-                       int zero_words, int32_t* __restrict__ tot_atomic, float* __restrict__ clear_rows) {
+                       int zero_words, float* __restrict__ clear_rows) {
   extern __shared__ int hist[];
-  if ((int)blockIdx.x < NB) {
-    bin_count_body((int)blockIdx.x, xy, P, per_block, tile_shift, NB, blockhist, hist, tot_atomic);
+  if ((int)blockIdx.x < j.NB) {
+    bin_count_block((int)blockIdx.x, j, hist);
     return;
   }
-  vertex_ride_block<F, VT, TT>((int)blockIdx.x - NB, tables, vert_idx, vert_w, n_ls, G, dG_zero, Ls, T, K, vstride, NV, pow2, vtot, zero_words,
+  vertex_ride_block<F, VT, TT>((int)blockIdx.x - j.NB, tables, vert_idx, vert_w, n_ls, G, dG_zero, Ls, T, K, vstride, NV, pow2, vtot, zero_words,
                                clear_rows);
 }
 
@@ -1081,10 +984,10 @@ struct VertexSrc {
   bool pow2;
 };
 
-// The COUNT of the NEXT batch's binning riding on the forward launch: workgroups [0, NB) run bin_count_body on that batch's
-// coordinates (histogram per block + the tile totals in global atomics of its persistent workspace) instead of a work item.
+// The COUNT of the NEXT batch's binning riding on the forward launch (`cride`, the reserving form): workgroups [nwork, nwork + NB)
+// run bin_count_reserve_block on that batch's coordinates (histogram, reservation on the running cursors, and in the last one out the
+// tile tables) instead of a work item.
 // The forward is bound by its 128 MiB of enc stores; the count reads 8 MiB and works in LDS atomics.  NB = 0: none.
-typedef BinJobDev BinCountRide;   // (the reserving count: bin_count_reserve_body)
 
 template <int SRC>
 __device__ __forceinline__ v2f vertex_value(const VertexSrc& vs, int l, int gx, int gy, int64_t goff, int gw) {
@@ -1110,7 +1013,7 @@ template <bool L16, int U, int SRC = 0>
 __global__ void __launch_bounds__(kTBF)
 tiled_fwd_il_kernel(const float4* __restrict__ sorted, const int4* __restrict__ items, const int32_t* __restrict__ n_items,
                     int32_t* __restrict__ counter, const int32_t* __restrict__ n_ls, const VertexSrc vs,
-                    float* __restrict__ enc, int L, int Ls, int tile_shift, int nwork, const BinCountRide cride) {
+                    float* __restrict__ enc, int L, int Ls, int tile_shift, int nwork, const BinJobDev cride) {
   constexpr int F = 2;
   extern __shared__ float2 img_raw[];             // [rows][kIL]: (feature 0, feature 1) of vertex `row` of level `column`
   v2f* img = reinterpret_cast<v2f*>(img_raw);
@@ -1119,9 +1022,7 @@ tiled_fwd_il_kernel(const float4* __restrict__ sorted, const int4* __restrict__ 
   // 768 places), so the launch lasts as long as its slowest item; riders placed first took 128 of those places and sent 30 items
   // into a second round (41.3 us), riders placed last take the ~100 free places at once and the rest as items retire (40.1 us).
   if ((int)blockIdx.x >= nwork) {
-    const int rb = (int)blockIdx.x - nwork;
-    if (rb == 0 && threadIdx.x == 0) cride.pws[2 * (1 << (2 * cride.tile_shift)) + 1] = 0;      // the scatter riders' task counter
-    bin_count_reserve_body<kTBF>(rb, cride, reinterpret_cast<int*>(img_raw));
+    bin_count_reserve_block<kTBF>((int)blockIdx.x - nwork, cride, reinterpret_cast<int*>(img_raw));
     return;
   }
   const int wg = (int)blockIdx.x;
@@ -1307,13 +1208,12 @@ tiled_fwd_il_kernel(const float4* __restrict__ sorted, const int4* __restrict__ 
 // grid with global integer atomics (fire and forget: they drain while other workgroups compute) — no partial images, no gather
 // pass; the sums are exact and order-free, so the vertex-grid gradient is bitwise reproducible.  dG64[vtot * F] = the scale S,
 // dG64[vtot * F + 1] != 0: poisoned (non-finite gradient or broken promise) — read by the kernels that turn dG64 into fp32.
-// The SCATTER of the NEXT batch's binning (bin_scatter2_body; its count rode on the forward launch: BinCountRide) as tasks the
+// The SCATTER of the NEXT batch's binning (`bride`: bin_scatter3_block; its count rode on the forward launch) as tasks the
 // persistent workgroups claim from a counter once their own work items are done.  The items are about equally heavy and there
 // are 2.6 of them per workgroup at the headline shape, so two workgroups in five finish a third of the launch early: the
 // tasks run in that hole instead of in two launches of their own at the head of the next step (binning depends on the
 // coordinates only, and the batches of an epoch are fixed slices of one permutation, known in advance: functions.py:186-194).
-// No task waits for another one (the totals were completed by the previous launch); NB = 0: none.
-typedef BinJobDev BinScatterRide;   // (bin_scatter3_body)
+// No task waits for another one (the tables were completed by the previous launch); NB = 0: none.
 
 // HDT (spatial-hash index source on a single rank, bound on |genc| given: round 5): the vertex stage backward is GONE.  The store
 // pass converts the item's exact 64-bit sums to fp32 (one rounding) and adds them straight to row hash(gx, gy) of the level's
@@ -1329,7 +1229,7 @@ tiled_bwd_il_kernel(const float4* __restrict__ sorted, const int4* __restrict__ 
                     int32_t* __restrict__ counter, const int32_t* __restrict__ n_ls, const float* __restrict__ genc,
                     float* __restrict__ dG, float* __restrict__ partials, const float* __restrict__ gmax_hint, int hint_count,
                     int hint_stride, int L, int Ls, int tile_shift, int lds_floats, int rows2, int log2_chunk, int nwork,
-                    RideAlong ride, MseRide mride, unsigned long long* __restrict__ dG64, const BinScatterRide bride,
+                    RideAlong ride, MseRide mride, unsigned long long* __restrict__ dG64, const BinJobDev bride,
                     float* __restrict__ hash_dt = nullptr, int64_t hash_T = 0, bool hash_pow2 = false) {
   constexpr int F = 2;
   extern __shared__ unsigned long long accil[];   // [rows2][kIL], then the compact fp32 image of the store pass
@@ -1629,7 +1529,7 @@ tiled_bwd_il_kernel(const float4* __restrict__ sorted, const int4* __restrict__ 
   }
   if (bride.NB > 0) {
     // the next batch's scatter tasks, claimed one at a time (the accumulator image is free: its LDS holds the task's cursors)
-    static_assert(kTB == kBinThreads, "bin_scatter3_body is written for the binning kernels' workgroup size");
+    static_assert(kTB == kBinThreads, "bin_scatter3_block is written for the binning kernels' workgroup size");
     int* sh = reinterpret_cast<int*>(accil);
     const int ntiles_b = 1 << (2 * bride.tile_shift);
     int32_t* claim = bride.pws + 2 * ntiles_b + 1;
@@ -1639,7 +1539,7 @@ tiled_bwd_il_kernel(const float4* __restrict__ sorted, const int4* __restrict__ 
       __syncthreads();
       const int task = s_task;
       if (task >= bride.NB) break;
-      bin_scatter3_body(task, bride, sh);
+      bin_scatter3_block(task, bride, sh);
     }
   }
 }
@@ -1956,35 +1856,64 @@ using namespace gngf;
     default: return (int)hipErrorInvalidValue;      \
   }
 
-// Bins P pixels into 4^tile_shift spatial tiles.  NB = number of binning blocks (<= 512), chunk = max pixels per
+// ---- binning launchers
+// The device form of one job, from a gngf_bin_job (the loose C arguments of gngf_bin_pixels / gngf_encode_tiled_prepare are put into
+// one first): owns the argument checks and per_block.  `reserving`: the form that needs the persistent counters and a pixel.
+static bool bin_job_dev(const gngf_bin_job* j, bool reserving, BinJobDev* d) {
+  if (!j || j->P < 0 || j->P >= (1ll << 31) || j->tile_shift < 0 || j->tile_shift > 6 || j->NB <= 0 || j->NB > kBinMaxBlocks || j->chunk <= 0)
+    return false;
+  if (!(j->xy && j->blockhist && j->tile_off && j->tile_item_base && j->items && j->n_items && j->sorted)) return false;
+  if (reserving && !(j->P > 0 && j->persistent_ws)) return false;
+  d->xy = reinterpret_cast<const float2*>(j->xy); d->P = j->P;
+  d->per_block = ceil_div(ceil_div(j->P, j->NB), kBinThreads) * kBinThreads;
+  d->NB = j->NB; d->tile_shift = j->tile_shift; d->chunk = j->chunk;
+  d->blockhist = j->blockhist; d->pws = j->persistent_ws; d->tile_off = j->tile_off; d->tile_item_base = j->tile_item_base;
+  d->items = reinterpret_cast<int4*>(j->items); d->n_items = j->n_items; d->sorted = reinterpret_cast<float4*>(j->sorted);
+  return true;
+}
+static BinJobDev bin_job_none() {
+  BinJobDev d = {nullptr, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  return d;
+}
+// dynamic LDS of a count block of the reserving form with NT threads (bin_count_reserve_block), and of every other binning block
+static size_t bin_reserve_lds(int tile_shift, int NT) { return (sizeof(int) << (2 * tile_shift)) + sizeof(int) * (2 * (NT / 64) + 1); }
+static size_t bin_lds(int tile_shift) { return sizeof(int) << (2 * tile_shift); }
+
+// a buffer cleared by rider workgroups of a count launch: zero_floats floats, a multiple of 4, 16-byte aligned (NULL: none)
+static bool zero_fill_ok(const float* zero_fill, int64_t zero_floats) {
+  return !zero_fill || (zero_floats >= 0 && (zero_floats & 3) == 0 && (reinterpret_cast<uintptr_t>(zero_fill) & 15) == 0);
+}
+static int zero_fill_blocks(int64_t nvec) { return nvec > 0 ? (int)(ceil_div(nvec, 4096) < 1024 ? ceil_div(nvec, 4096) : 1024) : 0; }
+
+// the scans of the four-launch form: rows of blockhist, then tiles
+static void launch_bin_scans(const BinJobDev& j, hipStream_t s) {
+  bin_rowscan_kernel<<<dim3((unsigned)ceil_div(1 << (2 * j.tile_shift), 4)), dim3(256), 0, s>>>(j);
+  bin_scan_kernel<<<dim3(1), dim3(kBinThreads), 0, s>>>(j);
+}
+
+// Bins P pixels into 4^tile_shift spatial tiles (the four-launch form).  NB = number of binning blocks (<= 512), chunk = max pixels per
 // work item.  Outputs: sorted (P float4 = x, y, bits(original index), 0), items (max_items int4 = start, count,
 // tile, items of that tile; max_items >= ceil(P/chunk) + 4^tile_shift), n_items (4: the count + three work counters), tile_off and tile_item_base
 // (4^tile_shift + 1 each: exclusive prefixes of pixels / items per tile), blockhist (4^tile_shift * (NB + 1) scratch).
 extern "C" int gngf_bin_pixels(const float* xy, int64_t P, int tile_shift, int NB, int chunk, int32_t* blockhist,
                                int32_t* tile_off, int32_t* tile_item_base, int32_t* items, int32_t* n_items, float* sorted,
                                void* stream) {
-  GNGF_CHECK_ARG(P >= 0 && P < (1ll << 31) && tile_shift >= 0 && tile_shift <= 6 && NB > 0 && NB <= kBinMaxBlocks && chunk > 0);
-  GNGF_CHECK_ARG(xy && blockhist && tile_off && tile_item_base && items && n_items && sorted);
-  const int ntiles = 1 << (2 * tile_shift);
-  const int64_t per_block = ceil_div(ceil_div(P, NB), kBinThreads) * kBinThreads;
+  const gngf_bin_job job = {xy, P, tile_shift, NB, chunk, blockhist, nullptr, tile_off, tile_item_base, items, n_items, sorted};
+  BinJobDev j;
+  GNGF_CHECK_ARG(bin_job_dev(&job, false, &j));
   hipStream_t s = as_stream(stream);
-  const size_t smem = (size_t)ntiles * sizeof(int);
-  bin_count_kernel<<<dim3(NB), dim3(kBinThreads), smem, s>>>(reinterpret_cast<const float2*>(xy), P, per_block, tile_shift, NB,
-                                                             blockhist);
-  // row totals live behind the NB columns of blockhist: the caller's scratch is 4^tile_shift * (NB + 1) int32
-  int32_t* tot = blockhist + (int64_t)ntiles * NB;
-  bin_rowscan_kernel<<<dim3((unsigned)ceil_div(ntiles, 4)), dim3(256), 0, s>>>(blockhist, NB, ntiles, tot);
-  bin_scan_kernel<<<dim3(1), dim3(kBinThreads), 0, s>>>(tot, tile_shift, chunk, tile_off, tile_item_base,
-                                                         reinterpret_cast<int4*>(items), n_items);
-  bin_scatter_kernel<<<dim3(NB), dim3(kBinThreads), smem, s>>>(reinterpret_cast<const float2*>(xy), P, per_block, tile_shift, NB,
-                                                               blockhist, tile_off, reinterpret_cast<float4*>(sorted));
+  bin_count_kernel<<<dim3(NB), dim3(kBinThreads), bin_lds(tile_shift), s>>>(j);
+  launch_bin_scans(j, s);
+  bin_scatter_kernel<<<dim3(NB), dim3(kBinThreads), bin_lds(tile_shift), s>>>(j);
   GNGF_RETURN_LAUNCH();
 }
 
-// Everything in front of the pixel stage in FOUR launches of one chain: binning (as gngf_bin_pixels) with the vertex stage
-// forward (as gngf_vertex_grid_fwd, levels [0, Ls)) riding on the count launch and two buffer clears riding along:
-// dG_zero (the vertex-grid gradient, same shape as G; NULL: none) is cleared by the vertex riders, zero_fill (zero_floats
-// floats, a multiple of 4, 16-byte aligned; NULL: none) by riders of the scatter launch.
+// Everything in front of the pixel stage in one chain: binning with the vertex stage forward (as gngf_vertex_grid_fwd, levels
+// [0, Ls)) and two buffer clears riding along: dG_zero (the vertex-grid gradient, same shape as G; NULL: none) is cleared by the
+// vertex riders, zero_fill (NULL: none) by riders of the count launch.
+//   no zero_fill, persistent_ws:     bin_count_vride > bin_scatter2                            (the two-launch "prepare" form)
+//   no zero_fill, no persistent_ws:  bin_count_vride > bin_rowscan > bin_scan > bin_scatter    (four-launch)
+//   zero_fill:                       bin_count_ride > bin_rowscan > bin_scan > bin_scatter_ride (four-launch; persistent_ws is not used)
 extern "C" int gngf_encode_tiled_prepare(const float* xy, int64_t P, int tile_shift, int NB, int chunk, int32_t* blockhist,
                                          int32_t* tile_off, int32_t* tile_item_base, int32_t* items, int32_t* n_items,
                                          float* sorted, const void* tables, int feat_dtype, const int32_t* vert_idx,
@@ -1996,64 +1925,50 @@ extern "C" int gngf_encode_tiled_prepare(const float* xy, int64_t P, int tile_sh
   // clear_rows (optional, spatial-hash source only): an (L,T,F) fp32 table gradient that lives from step to step — the vertex riders
   // zero row hash(gx, gy) of every staged vertex's level on the way (gngf_clear_hashed_rows without a launch of its own)
   GNGF_CHECK_ARG(!clear_rows || (mode == GNGF_MODE_HASH && (reinterpret_cast<uintptr_t>(clear_rows) & 3) == 0));
-  GNGF_CHECK_ARG(P >= 0 && P < (1ll << 31) && tile_shift >= 0 && tile_shift <= 6 && NB > 0 && NB <= kBinMaxBlocks && chunk > 0);
-  GNGF_CHECK_ARG(xy && blockhist && tile_off && tile_item_base && items && n_items && sorted);
   // G == NULL (spatial-hash source only): no vertex grid is wanted — the pixel stage gathers from the level tables itself
   // (gngf_encode_tiled_fwd_fused) — and the riders only clear (dG_zero / clear_rows), or do not run at all
   GNGF_CHECK_ARG(Ls > 0 && Ls <= GNGF_MAX_LEVELS && T > 0 && tables && n_ls && n_ls_host && (G || mode == GNGF_MODE_HASH));
   GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0));
-  GNGF_CHECK_ARG(!zero_fill || (zero_floats >= 0 && (zero_floats & 3) == 0 && (reinterpret_cast<uintptr_t>(zero_fill) & 15) == 0));
-  const int ntiles = 1 << (2 * tile_shift);
-  const int64_t per_block = ceil_div(ceil_div(P, NB), kBinThreads) * kBinThreads;
+  GNGF_CHECK_ARG(zero_fill_ok(zero_fill, zero_floats));
+  const int64_t nvec = zero_fill ? zero_floats / 4 : 0;
+  const int zblocks = zero_fill_blocks(nvec);
+  // (the counters of the "prepare" form are only touched by a chain that ends in bin_scatter2, which leaves them zero)
+  const gngf_bin_job job = {xy, P, tile_shift, NB, chunk, blockhist, zblocks == 0 ? persistent_ws : nullptr,
+                            tile_off, tile_item_base, items, n_items, sorted};
+  BinJobDev j;
+  GNGF_CHECK_ARG(bin_job_dev(&job, false, &j));
   hipStream_t s = as_stream(stream);
-  const size_t smem = (size_t)ntiles * sizeof(int);
+  const size_t smem = bin_lds(tile_shift);
   int64_t vtot = 0;
   for (int l = 0; l < Ls; ++l) vtot += (int64_t)(n_ls_host[l] + 2) * (n_ls_host[l] + 2);
   const int vblocks = (G || dG_zero || clear_rows) ? (int)ceil_div(vtot, kBinThreads) : 0;
   const bool pow2 = (T & (T - 1)) == 0;
-  const float2* xy2 = reinterpret_cast<const float2*>(xy);
-  const int64_t nvec = zero_fill ? zero_floats / 4 : 0;
-  const int zblocks = nvec > 0 ? (int)(ceil_div(nvec, 4096) < 1024 ? ceil_div(nvec, 4096) : 1024) : 0;
-  int32_t* tot = blockhist + (int64_t)ntiles * NB;
+  const bool hash = mode == GNGF_MODE_HASH;
+  const dim3 ride_grid((unsigned)(NB + vblocks)), block(kBinThreads);
+#define VERTEX_RIDE_ARGS static_cast<const TT*>(tables), vert_idx, vert_w, n_ls, G, dG_zero, Ls, T, K, vstride, NV, pow2, vtot, dG_zero_words, clear_rows
   if (zblocks == 0) {
     // no gradient clear on this launch: the vertex riders move to the COUNT launch and the scatter launch runs alone
-    if (mode == GNGF_MODE_HASH) {
-      DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_count_vride_kernel<kF, false, TT><<<dim3((unsigned)(NB + vblocks)), dim3(kBinThreads), smem, s>>>(
-                                  xy2, P, per_block, tile_shift, NB, blockhist, static_cast<const TT*>(tables), nullptr, nullptr, n_ls, G,
-                                  dG_zero, Ls, T, 0, 0, 0, pow2, vtot, dG_zero_words, persistent_ws, clear_rows))));
+    if (hash) {
+      DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_count_vride_kernel<kF, false, TT><<<ride_grid, block, smem, s>>>(j, VERTEX_RIDE_ARGS))));
     } else {
-      DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_count_vride_kernel<kF, true, TT><<<dim3((unsigned)(NB + vblocks)), dim3(kBinThreads), smem, s>>>(
-                                  xy2, P, per_block, tile_shift, NB, blockhist, static_cast<const TT*>(tables), vert_idx, vert_w, n_ls, G,
-                                  dG_zero, Ls, T, K, vstride, NV, pow2, vtot, dG_zero_words, persistent_ws, nullptr))));
+      DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_count_vride_kernel<kF, true, TT><<<ride_grid, block, smem, s>>>(j, VERTEX_RIDE_ARGS))));
     }
-    if (persistent_ws) {       // count -> scatter: the scans ride inside the scatter launch (bin_scatter2_kernel)
-      bin_scatter2_kernel<<<dim3(NB), dim3(kBinThreads), smem, s>>>(xy2, P, per_block, tile_shift, NB, chunk, blockhist, persistent_ws,
-                                                                   tile_off, tile_item_base, reinterpret_cast<int4*>(items), n_items,
-                                                                   reinterpret_cast<float4*>(sorted));
-      GNGF_RETURN_LAUNCH();
+    if (j.pws) {
+      bin_scatter2_kernel<<<dim3(NB), block, smem, s>>>(j);
+    } else {
+      launch_bin_scans(j, s);
+      bin_scatter_kernel<<<dim3(NB), block, smem, s>>>(j);
     }
-    bin_rowscan_kernel<<<dim3((unsigned)ceil_div(ntiles, 4)), dim3(256), 0, s>>>(blockhist, NB, ntiles, tot);
-    bin_scan_kernel<<<dim3(1), dim3(kBinThreads), 0, s>>>(tot, tile_shift, chunk, tile_off, tile_item_base,
-                                                           reinterpret_cast<int4*>(items), n_items);
-    bin_scatter_kernel<<<dim3(NB), dim3(kBinThreads), smem, s>>>(xy2, P, per_block, tile_shift, NB, blockhist, tile_off,
-                                                                 reinterpret_cast<float4*>(sorted));
     GNGF_RETURN_LAUNCH();
   }
-  bin_count_ride_kernel<<<dim3((unsigned)(NB + zblocks)), dim3(kBinThreads), smem, s>>>(xy2, P, per_block, tile_shift, NB, blockhist,
-                                                                                       reinterpret_cast<float4*>(zero_fill), nvec, zblocks);
-  bin_rowscan_kernel<<<dim3((unsigned)ceil_div(ntiles, 4)), dim3(256), 0, s>>>(blockhist, NB, ntiles, tot);
-  bin_scan_kernel<<<dim3(1), dim3(kBinThreads), 0, s>>>(tot, tile_shift, chunk, tile_off, tile_item_base,
-                                                         reinterpret_cast<int4*>(items), n_items);
-  float4* sorted4 = reinterpret_cast<float4*>(sorted);
-  if (mode == GNGF_MODE_HASH) {
-    DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_scatter_ride_kernel<kF, false, TT><<<dim3((unsigned)(NB + vblocks)), dim3(kBinThreads), smem, s>>>(
-                                xy2, P, per_block, tile_shift, NB, blockhist, tile_off, sorted4, static_cast<const TT*>(tables), nullptr,
-                                nullptr, n_ls, G, dG_zero, Ls, T, 0, 0, 0, pow2, vtot, dG_zero_words, clear_rows))));
+  bin_count_ride_kernel<<<dim3((unsigned)(NB + zblocks)), block, smem, s>>>(j, reinterpret_cast<float4*>(zero_fill), nvec, zblocks);
+  launch_bin_scans(j, s);
+  if (hash) {
+    DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_scatter_ride_kernel<kF, false, TT><<<ride_grid, block, smem, s>>>(j, VERTEX_RIDE_ARGS))));
   } else {
-    DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_scatter_ride_kernel<kF, true, TT><<<dim3((unsigned)(NB + vblocks)), dim3(kBinThreads), smem, s>>>(
-                                xy2, P, per_block, tile_shift, NB, blockhist, tile_off, sorted4, static_cast<const TT*>(tables), vert_idx,
-                                vert_w, n_ls, G, dG_zero, Ls, T, K, vstride, NV, pow2, vtot, dG_zero_words, nullptr))));
+    DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_scatter_ride_kernel<kF, true, TT><<<ride_grid, block, smem, s>>>(j, VERTEX_RIDE_ARGS))));
   }
+#undef VERTEX_RIDE_ARGS
   GNGF_RETURN_LAUNCH();
 }
 
@@ -2154,24 +2069,6 @@ static bool interleaved_applies(const int32_t* n_ls_host, int Ls, int F, int til
   return bytes <= (backward ? 112 : 72) * 1024;
 }
 
-static bool bin_job_ok(const gngf_bin_job* j) {
-  return j && j->xy && j->P > 0 && j->P < (1ll << 31) && j->tile_shift >= 0 && j->tile_shift <= 6 && j->NB > 0 && j->NB <= kBinMaxBlocks &&
-         j->chunk > 0 && j->blockhist && j->persistent_ws && j->tile_off && j->tile_item_base && j->items && j->n_items && j->sorted;
-}
-static int64_t bin_per_block(int64_t P, int NB) { return ceil_div(ceil_div(P, NB), kBinThreads) * kBinThreads; }
-static BinJobDev bin_job_dev(const gngf_bin_job* j) {
-  BinJobDev d;
-  d.xy = reinterpret_cast<const float2*>(j->xy); d.P = j->P; d.per_block = bin_per_block(j->P, j->NB);
-  d.NB = j->NB; d.tile_shift = j->tile_shift; d.chunk = j->chunk;
-  d.blockbase = j->blockhist; d.pws = j->persistent_ws; d.tile_off = j->tile_off; d.tile_item_base = j->tile_item_base;
-  d.items = reinterpret_cast<int4*>(j->items); d.n_items = j->n_items; d.sorted = reinterpret_cast<float4*>(j->sorted);
-  return d;
-}
-static BinJobDev bin_job_none() {
-  BinJobDev d = {nullptr, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  return d;
-}
-
 // The launcher's own decision, for callers that size / initialise buffers differently for the two kernel families (the
 // fixed-point vertex grid dG64 is only filled by the interleaved backward): 1 = the level-interleaved kernel will run.
 extern "C" int gngf_tiled_interleaved_applies(const int32_t* n_ls_host, int Ls, int F, int tile_shift, int lds_bytes, int backward) {
@@ -2193,15 +2090,11 @@ extern "C" int gngf_encode_tiled_fwd(const float* sorted, const int32_t* items, 
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
       if (e != hipSuccess) return (int)e;
     }
-    // persistent workgroups: as many as fit the chip at once (LDS-bound), sharing the items through a counter
-    const int per_cu = (int)((150 * 1024) / (smem + 2048)) < 1 ? 1 : (int)((150 * 1024) / (smem + 2048));
-    (void)per_cu;
     const int nwork = max_items;                   // forward: one item per workgroup (two to three workgroups share a CU)
     const VertexSrc vs = {G, nullptr, nullptr, nullptr, 0, 0, 0, 0, false};
-    const BinCountRide none = bin_job_none();
     fn<<<dim3((unsigned)nwork), dim3(kTBF), smem, as_stream(stream)>>>(
         reinterpret_cast<const float4*>(sorted), reinterpret_cast<const int4*>(items), n_items, const_cast<int32_t*>(n_items) + 1, n_ls, vs,
-        enc, L, Ls, tile_shift, nwork, none);
+        enc, L, Ls, tile_shift, nwork, bin_job_none());
     GNGF_RETURN_LAUNCH();
   }
   DISPATCH_F(F, {
@@ -2217,22 +2110,19 @@ extern "C" int gngf_encode_tiled_fwd(const float* sorted, const int32_t* items, 
   GNGF_RETURN_LAUNCH();
 }
 
-// Binning alone in TWO launches (count -> scatter, the scans ride inside the scatter launch: bin_scatter2_kernel) — the form the
-// step uses when the vertex stage forward is fused into the pixel stage (gngf_encode_tiled_fwd_fused) and nothing else has to
-// ride on the binning.  zero_fill (optional; zero_floats floats, a multiple of 4, 16-byte aligned): cleared by rider workgroups
-// of the count launch.
+// Binning alone in TWO launches, the reserving form (bin_count_reserve > bin_scatter3) — what the step uses when the vertex stage
+// forward is fused into the pixel stage (gngf_encode_tiled_fwd_fused) and no rider of an earlier step has binned the batch.
+// zero_fill (optional): cleared by rider workgroups of the count launch.
 extern "C" int gngf_bin_pixels2(const gngf_bin_job* job, float* zero_fill, int64_t zero_floats, void* stream) {
-  GNGF_CHECK_ARG(bin_job_ok(job));
-  GNGF_CHECK_ARG(!zero_fill || (zero_floats >= 0 && (zero_floats & 3) == 0 && (reinterpret_cast<uintptr_t>(zero_fill) & 15) == 0));
-  const int ntiles = 1 << (2 * job->tile_shift);
+  BinJobDev j;
+  GNGF_CHECK_ARG(bin_job_dev(job, true, &j));
+  GNGF_CHECK_ARG(zero_fill_ok(zero_fill, zero_floats));
   hipStream_t s = as_stream(stream);
-  const BinJobDev j = bin_job_dev(job);
   const int64_t nvec = zero_fill ? zero_floats / 4 : 0;
-  const int zblocks = nvec > 0 ? (int)(ceil_div(nvec, 4096) < 1024 ? ceil_div(nvec, 4096) : 1024) : 0;
-  const size_t smem_c = ((size_t)ntiles + 2 * (kBinThreads / 64) + 1) * sizeof(int);
-  bin_count_reserve_kernel<<<dim3((unsigned)(job->NB + zblocks)), dim3(kBinThreads), smem_c, s>>>(
-      j, reinterpret_cast<float4*>(zero_fill), nvec, zblocks > 0 ? zblocks : 1);
-  bin_scatter3_kernel<<<dim3(job->NB), dim3(kBinThreads), (size_t)ntiles * sizeof(int), s>>>(j);
+  const int zblocks = zero_fill_blocks(nvec);
+  bin_count_reserve_kernel<<<dim3((unsigned)(j.NB + zblocks)), dim3(kBinThreads), bin_reserve_lds(j.tile_shift, kBinThreads), s>>>(
+      j, reinterpret_cast<float4*>(zero_fill), nvec, zblocks);
+  bin_scatter3_kernel<<<dim3(j.NB), dim3(kBinThreads), bin_lds(j.tile_shift), s>>>(j);
   GNGF_RETURN_LAUNCH();
 }
 
@@ -2240,15 +2130,16 @@ extern "C" int gngf_bin_pixels2(const gngf_bin_job* job, float* zero_fill, int64
 // tables, <= 16 staged levels whose image fits the LDS — gngf_tiled_interleaved_applies(…, 0) — anything else is rejected):
 // the staged sub-grids are gathered from the level tables themselves (mode / vert_idx / vert_w / vstride / NV as
 // gngf_vertex_grid_fwd), same arithmetic in the same order, so enc equals gngf_vertex_grid_fwd + gngf_encode_tiled_fwd bit for
-// bit.  next_count (optional): the COUNT half of another batch's binning (its per-block histograms and tile totals) runs in
-// extra workgroups at the head of this launch; its scatter half rides on gngf_encode_tiled_bwd(…, next_bin).
+// bit.  next_count (optional): the COUNT half of another batch's binning, reserving form (reservations per block, tile tables) runs
+// in extra workgroups at the end of this launch's grid; its scatter half rides on gngf_encode_tiled_bwd(…, next_bin).
 extern "C" int gngf_encode_tiled_fwd_fused(const float* sorted, const int32_t* items, const int32_t* n_items, int max_items,
                                            const int32_t* n_ls, const int32_t* n_ls_host, const void* tables, int feat_dtype,
                                            const int32_t* vert_idx, const float* vert_w, float* enc, int L, int Ls, int F, int64_t T,
                                            int K, int mode, int vstride, int64_t NV, int tile_shift, int lds_bytes,
                                            const gngf_bin_job* next_count, void* stream) {
   GNGF_CHECK_ARG(max_items >= 0 && L > 0 && Ls > 0 && Ls <= L && L <= GNGF_MAX_LEVELS && lds_bytes >= 0 && lds_bytes <= 128 * 1024);
-  GNGF_CHECK_ARG(!next_count || bin_job_ok(next_count));
+  BinJobDev cride = bin_job_none();
+  GNGF_CHECK_ARG(!next_count || bin_job_dev(next_count, true, &cride));
   if (max_items == 0 && !next_count) return 0;
   GNGF_CHECK_ARG(sorted && items && n_items && n_ls && n_ls_host && tables && enc && T > 0);
   GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0));
@@ -2271,10 +2162,8 @@ extern "C" int gngf_encode_tiled_fwd_fused(const float* sorted, const int32_t* i
   }
   GNGF_CHECK_ARG(feat_dtype == GNGF_FEAT_F32);
   size_t smem = (size_t)interleaved_rows(n_ls_host, Ls, tile_shift) * kIL * 8;
-  BinCountRide cride = bin_job_none();
   if (next_count) {
-    cride = bin_job_dev(next_count);
-    const size_t hist = (sizeof(int) << (2 * next_count->tile_shift)) + sizeof(int) * (2 * (kTBF / 64) + 1);
+    const size_t hist = bin_reserve_lds(cride.tile_shift, kTBF);
     smem = smem < hist ? hist : smem;
   }
   const bool hash = mode == GNGF_MODE_HASH;
@@ -2304,7 +2193,8 @@ extern "C" int gngf_encode_tiled_bwd(const float* sorted, const int32_t* items, 
                                      void* dG64, int log2_pixels, const gngf_bin_job* next_bin, void* stream) {
   GNGF_CHECK_ARG(!hash_dtables || hash_T > 0);
   // the scatter half of another batch's binning rides in the tail of the persistent interleaved kernel only
-  GNGF_CHECK_ARG(!next_bin || (bin_job_ok(next_bin) && max_items > 0 && n_ls_host &&
+  BinJobDev bride = bin_job_none();
+  GNGF_CHECK_ARG(!next_bin || (bin_job_dev(next_bin, true, &bride) && max_items > 0 && n_ls_host &&
                                interleaved_applies(n_ls_host, Ls, F, tile_shift, lds_bytes / 4, true)));
   const bool hpow2 = hash_dtables && (hash_T & (hash_T - 1)) == 0;
   GNGF_CHECK_ARG(max_items >= 0 && L > 0 && Ls > 0 && Ls <= L && L <= GNGF_MAX_LEVELS && lds_bytes >= 0 && lds_bytes <= 64 * 1024);
@@ -2351,10 +2241,8 @@ extern "C" int gngf_encode_tiled_bwd(const float* sorted, const int32_t* items, 
   if (max_items > 0 && interleaved_applies(n_ls_host, Ls, F, tile_shift, lds_bytes / 4, true)) {
     const int rows2 = 2 * interleaved_rows(n_ls_host, Ls, tile_shift);
     size_t smem = (size_t)rows2 * kIL * 8 + (size_t)lds_bytes;          // accumulators + the compact fp32 image of the store pass
-    BinScatterRide bride = bin_job_none();
     if (next_bin) {
-      bride = bin_job_dev(next_bin);
-      const size_t need = (sizeof(int) << (2 * next_bin->tile_shift)) + sizeof(int);
+      const size_t need = bin_lds(bride.tile_shift) + sizeof(int);
       smem = smem < need ? need : smem;
     }
     // spatial-hash source and neither vertex grid handed in: the store pass adds to the table gradient itself

@@ -1169,9 +1169,14 @@ _BIN_WORKSPACES = {}
 
 
 def _bin_workspace(dev, ntiles, owner=None, kind="prepare"):
-    """Persistent zero-initialised counters of the two-launch binning (tile totals, tile cursors, a ticket).  The kernels put
-    them back to zero themselves, so one buffer serves every step — including every replay of a captured step (it is allocated
-    at warm-up, outside the capture).  It belongs to ONE sequence of steps: `owner` is the model's DataParallel object (one per
+    """Persistent counters of the binning forms that take two launches or none of their own: 2 * ntiles + 3 int32, zero at their
+    first use, in one of two layouts (csrc/encode_tiled.hip, BinJobDev):
+      kind="prepare" (gngf_encode_tiled_prepare without a zero-fill): [tile totals | tile cursors | ticket | 2 unused] — the last
+        scatter block out puts them back to zero;
+      kind="reserve" (gngf_bin_pixels2 and the riders of the pixel-stage launches): [running tile cursors | their values at the start
+        of the current job | unused | task counter of the riding scatter | count ticket] — the cursors are never reset.
+    Either way one buffer serves every step — including every replay of a captured step (it is allocated at warm-up, outside the
+    capture).  It belongs to ONE sequence of steps: `owner` is the model's DataParallel object (one per
     model: two models stepping concurrently on two streams do not share counters); calls without an owner (the op used on its
     own) share one buffer per device and tiling and must not overlap in time."""
     store = owner.bin_ws if owner is not None else _BIN_WORKSPACES

@@ -109,11 +109,12 @@ int gngf_clear_hashed_rows(float* dtables, const int32_t* n_ls, int Ls, int F, i
  *   int32. */
 int gngf_bin_pixels(const float* xy, int64_t P, int tile_shift, int NB, int chunk, int32_t* blockhist, int32_t* tile_off,
                     int32_t* tile_item_base, int32_t* items, int32_t* n_items, float* sorted, void* stream);
-/* gngf_encode_tiled_prepare: everything in front of the pixel stage as ONE chain of four launches — gngf_bin_pixels plus
- *   gngf_vertex_grid_fwd (levels [0, Ls), riding on the count launch as extra workgroups) plus two buffer clears:
- *   dG_zero (same shape as G; NULL: none) and zero_fill (zero_floats floats, a multiple of 4, 16-byte aligned — the table
- *   gradient buffer; NULL: none; riding on the scatter launch).  Parallel branches of a replayed hipGraph cost ~10 us per
- *   cross-queue dependency on this stack; riders on one chain cost nothing.
+/* gngf_encode_tiled_prepare: everything in front of the pixel stage as ONE chain of launches — the binning of gngf_bin_pixels plus
+ *   gngf_vertex_grid_fwd (levels [0, Ls)) riding on it as extra workgroups plus two buffer clears: dG_zero (same shape as G; NULL:
+ *   none; cleared by the vertex riders) and zero_fill (zero_floats floats, a multiple of 4, 16-byte aligned — the table gradient
+ *   buffer; NULL: none).  Without zero_fill the vertex riders sit on the count launch; with it, zero_fill is cleared by riders of the
+ *   count launch and the vertex riders sit on the scatter launch (four launches).  Parallel branches of a replayed hipGraph cost
+ *   ~10 us per cross-queue dependency on this stack; riders on one chain cost nothing.
  *   G may be NULL for the spatial-hash source (round 5): no vertex grid is built — the pixel stage gathers from the level tables
  *   itself (gngf_encode_tiled_fwd_fused) — and the riders only clear (dG_zero / clear_rows), or do not run at all. */
 int gngf_encode_tiled_prepare(const float* xy, int64_t P, int tile_shift, int NB, int chunk, int32_t* blockhist,
@@ -122,9 +123,10 @@ int gngf_encode_tiled_prepare(const float* xy, int64_t P, int tile_shift, int NB
                               const int32_t* n_ls, const int32_t* n_ls_host, float* G, float* dG_zero, int dG_zero_words, int Ls,
                               int F, int64_t T, int K, int mode, int vstride, int64_t NV, float* zero_fill, int64_t zero_floats,
                               int32_t* persistent_ws, float* clear_rows, void* stream);
-/* persistent_ws (optional): (2 * 4^tile_shift + 1) int32, ZERO before its first use and owned by one stream — with it (and
- * without zero_fill) the binning is TWO launches instead of four: the tile totals meet in global atomics, every scatter
- * workgroup scans them itself, and the last one out puts the workspace back to zero. */
+/* persistent_ws (optional): (2 * 4^tile_shift + 1) int32 = [tile totals | tile cursors | ticket], ZERO before its first use and
+ * owned by one stream — with it (and without zero_fill) the binning is TWO launches instead of four: the tile totals meet in
+ * global atomics, every scatter workgroup scans them itself, and the last one out puts the workspace back to zero.  With zero_fill
+ * it is not touched. */
 /* clear_rows (optional, spatial-hash source only): an (L,T,F) fp32 table gradient kept from step to step — the vertex riders zero
  * row hash(gx, gy) of every staged vertex's level on the way (what gngf_clear_hashed_rows does, without a launch of its own). */
 /* dG_zero_words: 1 = dG_zero is the fp32 vertex-grid gradient (vtot * F floats); 2 = it is the 64-bit fixed-point form of
@@ -150,18 +152,20 @@ int gngf_vertex_grid_bwd(const void* tables, int feat_dtype, const int32_t* vert
  * tile_level_off (4^tile_shift * Ls int32, optional): float offset of level l's sub-grid inside tile t's image at
  * [t * Ls + l], -1 when the level does not fit (levels are laid out back to back in ascending order, a level that
  * would exceed lds_bytes is skipped); NULL: the gather pass re-derives it per vertex. */
-/* One binning job (the arguments of gngf_bin_pixels as a host struct): lets the binning of ANOTHER batch ride on the pixel-stage
- * launches of the current one — binning depends on the coordinates only, and the batches of an epoch are fixed slices of one
- * permutation, known in advance (functions.py:186-194).  persistent_ws: (2 * 4^tile_shift + 3) int32, ZERO before its first
- * use, owned by one sequence of steps and used by these entry points only (NOT shared with gngf_encode_tiled_prepare's): running
- * tile cursors, their values at the start of the current job, the count half's ticket, the task counter of the riding scatter —
- * never reset.  blockhist: 4^tile_shift * (NB + 1) int32 of scratch that carries each count block's reserved offsets to the
- * scatter block of the same index. */
+/* One binning job (the arguments of gngf_bin_pixels as a host struct) for the RESERVING form of the binning: gngf_bin_pixels2, or the
+ * binning of ANOTHER batch riding on the pixel-stage launches of the current one — binning depends on the coordinates only, and the
+ * batches of an epoch are fixed slices of one permutation, known in advance (functions.py:186-194).  A count workgroup reserves its
+ * places in every tile on running per-tile cursors, the last count workgroup out writes the tile tables and the work items, a scatter
+ * workgroup moves its pixels.  P > 0.  persistent_ws (required): (2 * 4^tile_shift + 3) int32 = [tile cursors | their values at the
+ * start of the current job | unused | task counter of the riding scatter | ticket of the count workgroups], ZERO before its first
+ * use and never reset, owned by one sequence of steps and used by these entry points only (NOT shared with
+ * gngf_encode_tiled_prepare's).  blockhist: scratch, used as [NB][4^tile_shift] int32 — each count workgroup's reserved offsets,
+ * for the scatter workgroup of the same index. */
 typedef struct gngf_bin_job {
   const float* xy;            /* (P, 2) coordinates of the batch to bin */
   int64_t P;
   int tile_shift, NB, chunk;
-  int32_t* blockhist;         /* 4^tile_shift * (NB + 1) scratch */
+  int32_t* blockhist;         /* 4^tile_shift * (NB + 1) scratch (the size gngf_bin_pixels needs: one workspace serves both) */
   int32_t* persistent_ws;
   int32_t* tile_off;          /* outputs, as gngf_bin_pixels */
   int32_t* tile_item_base;
@@ -169,13 +173,14 @@ typedef struct gngf_bin_job {
   int32_t* n_items;
   float* sorted;
 } gngf_bin_job;
-/* binning in two launches (count -> scatter with the scans inside); zero_fill (optional, zero_floats a multiple of 4, 16-byte
- * aligned) is cleared by rider workgroups of the count launch */
+/* the reserving form as two launches of its own (count + tile tables -> scatter); same outputs as gngf_bin_pixels, the order of
+ * the pixels inside a tile aside.  zero_fill (optional, zero_floats a multiple of 4, 16-byte aligned) is cleared by rider
+ * workgroups of the count launch */
 int gngf_bin_pixels2(const gngf_bin_job* job, float* zero_fill, int64_t zero_floats, void* stream);
 /* pixel stage forward with the vertex stage forward fused into its staging loop (bit-identical to gngf_vertex_grid_fwd +
  * gngf_encode_tiled_fwd).  Level-interleaved kernel (F = 2, fp32 tables — see gngf_tiled_interleaved_applies): both index sources;
  * generic kernel (any other shape; round 5): spatial-hash source, fp32 or fp16 tables, next_count must be NULL.
- * next_count (optional): the count half of another batch's binning runs in extra workgroups at the head of the launch; its
+ * next_count (optional): the count half of another batch's binning runs in extra workgroups at the end of the launch's grid; its
  * scatter half rides on gngf_encode_tiled_bwd(..., next_bin) of the same step. */
 int gngf_encode_tiled_fwd_fused(const float* sorted, const int32_t* items, const int32_t* n_items, int max_items,
                                 const int32_t* n_ls, const int32_t* n_ls_host, const void* tables, int feat_dtype,
