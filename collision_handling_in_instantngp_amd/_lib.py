@@ -91,6 +91,10 @@ SIGNATURES = {
     "gngf_adam_block_elems": [],
     "gngf_adam_step": [_P, _I, _L, _P, _P, _P, _I, _F, _F, _F, _F, _P],
     "gngf_adam_step_masked": [_P, _I, _L, _P, _P, _P, _I, _F, _F, _F, _F, _P, _P],
+    "gngf_image_scatter": [_P, _P, _P, _L, _L, _L, _I, _P],
+    "gngf_image_metrics_blocks": [_L],
+    "gngf_image_metrics_workspace_words": [_L],
+    "gngf_image_metrics": [_P, _P, _P, _P, _L, _P],
 }
 
 ABI_VERSION = 14

@@ -5,10 +5,12 @@ written against it finds the same names and conventions:
                                            row-major order, Y = channels / 255
   normalise / permutation                  main.py:50-58: x / (max(w, h) - 1); shuffled_indices and their inverse
   reassemble_image     functions.py:308,332-335: inverse permutation, (output * 255) -> int32 image (truncation)
+  reassemble_image_device                  the same image as a device tensor, written by the scatter kernel
   save_checkpoint / load_checkpoint        functions.py:761-781, models.py HPD/encoding weight paths: the five
                                            state-dict files of the reference, loadable in either direction
 
-Host-side numpy/torch only: nothing here touches the GPU kernels."""
+Host-side numpy/torch only, with one exception: reassemble_image_device runs the image scatter kernel (csrc/metrics.hip,
+through ops.image_scatter) and needs device tensors."""
 import os
 from typing import Optional, Tuple
 
@@ -98,6 +100,32 @@ def reassemble_image(outputs: torch.Tensor, reordered_indices: Optional[torch.Te
     out = outputs[reordered_indices.long()] if should_shuffle else outputs
     img = (out * 255).reshape((h, w, 3) if not should_bw else (h, w))
     return img.int().detach().cpu().numpy()
+
+
+def reassemble_image_device(outputs: torch.Tensor, reordered_indices: Optional[torch.Tensor], h: int, w: int,
+                            should_bw: bool = False, should_shuffle: bool = True) -> torch.Tensor:
+    """reassemble_image's result as a device int32 tensor, without the gather: with shuffled the inverse of
+    reordered_indices, img[shuffled[i]] = out[i] is what the scatter kernel writes (csrc/metrics.hip).  outputs: device
+    fp32, (h*w, 3) or, should_bw, h*w values."""
+    from . import ops
+    P = h * w
+    out = outputs.detach().reshape(P, -1)
+    if out.shape[1] != (1 if should_bw else 3):
+        raise ValueError(f"outputs {tuple(outputs.shape)} do not fill a {(h, w) if should_bw else (h, w, 3)} image")
+    out = out if out.is_contiguous() else out.contiguous()
+    shuffled = None
+    if should_shuffle:
+        ro = reordered_indices.reshape(-1).to(out.device).long()
+        # the kernel trusts its indices: reordered_indices must be a permutation of range(P)
+        if ro.numel() != P or int(ro.min()) < 0 or int(ro.max()) >= P:
+            raise ValueError(f"reordered_indices must be a permutation of range({P})")
+        shuffled = torch.full((P,), -1, dtype=torch.int32, device=out.device)
+        shuffled[ro] = torch.arange(P, dtype=torch.int32, device=out.device)
+        if int(shuffled.min()) < 0:
+            raise ValueError(f"reordered_indices must be a permutation of range({P})")
+    img = torch.empty((P, out.shape[1]), dtype=torch.int32, device=out.device)
+    ops.image_scatter(out, shuffled, img, 0)
+    return img.view((h, w) if should_bw else (h, w, 3))
 
 
 def save_checkpoint(net, optimizer, folder: str) -> dict:

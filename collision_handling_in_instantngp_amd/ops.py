@@ -1817,6 +1817,39 @@ def js_kl_rows(pbar, gamma, eps):
     return JsKlFunction.apply(pbar, gamma, eps)
 
 
+def image_scatter(out, perm, img, lo):
+    """img (P,C) int32, rows perm[lo:lo + n] (perm None: rows lo:lo + n) = (out * 255).int() for one batch's outputs out (n,C)
+    fp32 contiguous (csrc/metrics.hip).  perm (P) int32 must hold values in [0, P) only: the kernel does not check it."""
+    n, C = out.shape
+    P = img.shape[0]
+    if img.shape[1] != C:
+        raise ValueError(f"out has {C} channels, the image {img.shape[1]}")
+    if perm is not None and perm.numel() != P:
+        raise ValueError(f"perm has {perm.numel()} entries for an image of {P} pixels")
+    if n == 0:
+        return
+    call("gngf_image_scatter", ptr(out, _f32, "out"), ptr(perm, _i32, "perm"), ptr(img, _i32, "img"), int(lo), n, P, C,
+         stream_ptr())
+
+
+def image_metrics_workspace(n_elems, device):
+    """per-workgroup partial sums of image_metrics for n_elems elements (needs no clearing)"""
+    return torch.empty((query("gngf_image_metrics_workspace_words", n_elems),), dtype=_i64, device=device)
+
+
+def image_metrics(img, target, sums, workspace):
+    """sums (2,) int64 = (#{img == target}, sum (img - target)^2) of an int32 image and its uint8 target, exact
+    (csrc/metrics.hip).  No synchronisation."""
+    n = img.numel()
+    if target.numel() != n:
+        raise ValueError(f"image has {n} elements, the target {target.numel()}")
+    if sums.numel() != 2 or workspace.numel() < query("gngf_image_metrics_workspace_words", n):
+        raise ValueError("sums must hold 2 words and workspace gngf_image_metrics_workspace_words(n) words")
+    call("gngf_image_metrics", ptr(img, _i32, "img"), ptr(target, torch.uint8, "target"), ptr(sums, _i64, "sums"),
+         ptr(workspace, _i64, "workspace"), n, stream_ptr())
+    return sums
+
+
 # Keep the decoder's activated hidden layers (512 B / pixel) from forward to backward instead of recomputing them: the
 # stores and loads ride under the MFMAs of kernels that leave most of the HBM bandwidth unused (decoder backward 345 -> ~230 us
 # at 2^20 px).  False: recompute (no extra memory).

@@ -724,13 +724,18 @@ class GraphedStep:
 
 def train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_collisions, batch_percentage=1.0,
                 should_shuffle=True, shuffled_indices=None, previous_collisions=None, previous_min_possible_collisions=None,
-                should_calc_counts=False, graph=False):
+                should_calc_counts=False, graph=False, image=None):
     """The batch loop of the reference's train_step (functions.py:183-281): ceil(1/batch_percentage) mini-batches of
     zero_grad -> net -> Loss -> weighted sum -> backward -> step.  graph=True replays each step from a hipGraph
     (GraphedStep, cached on the net per batch shape).  Returns a dict of per-batch device tensors and the outputs /
-    indices in batch order; nothing is read back to the host inside the loop."""
+    indices in batch order; nothing is read back to the host inside the loop.  image: an EpochImage that receives every
+    batch's outputs (one launch after the step, outside any graph) — the epoch's image, accuracy and PSNR on the device."""
     net.train()
     shape = w * h
+    if image is not None:
+        if image.P != shape or (image.perm is not None) != bool(should_shuffle):
+            raise ValueError("image= was built for another image size, or with / without the permutation this epoch uses")
+        image.begin()
     num_batches = int(np.ceil(shape / (shape * batch_percentage)))
     step = int(batch_percentage * shape)
     dev = x.device
@@ -794,6 +799,8 @@ def train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_coll
             loss.backward(gradient=one.to(loss.dtype))
             optimizer.step()
         outputs[lo:lo + out.shape[0]] = out.detach()
+        if image is not None:
+            image.add(out.detach(), lo)
         if idx is not None:
             if indices is None:
                 indices = torch.zeros((shape, *idx.shape[1:]), dtype=idx.dtype, device=dev)
@@ -814,7 +821,7 @@ def train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_coll
 def train_step(net, loss_fn, optimizer, x, target, w, h, hash_table_size, topk_k, l_mse, l_js_kl, l_collisions,
                batch_percentage=1, num_levels=4, should_bw=False, should_calc_counts=False, should_shuffle=True,
                shuffled_indices=None, reordered_indices=None, previous_collisions=None,
-               previous_min_possible_collisions=None, *, graph=False):
+               previous_min_possible_collisions=None, *, graph=False, image=None):
     """reference functions.py:139-355 — same positional signature and the same 9-tuple:
         (loss, to_show_img (h,w,3) int32 numpy, collisions, min_possible_collisions, counts_per_level, mse,
          kl_div_losses (L,) | None, collisions_losses (L,) | None, indices_per_level)
@@ -822,14 +829,16 @@ def train_step(net, loss_fn, optimizer, x, target, w, h, hash_table_size, topk_k
     batch visits (int(batch_percentage * w * h) * num_batches < w * h) show as zeros where the reference shows
     uninitialised memory; collision statistics are taken over each pixel's own top-K indices (the reference allocates
     topk_k / batch_size index slots per pixel and fills topk_k of them, so its statistic is partly uninitialised memory —
-    SURVEY.md §8f.3).  graph=True (keyword-only, extension) replays every step from a hipGraph."""
+    SURVEY.md §8f.3).  graph=True (keyword-only, extension) replays every step from a hipGraph.  image= (keyword-only,
+    extension): an EpochImage that collects the epoch's image on the device; position 1 of the tuple is then None — no gather,
+    cast or host copy of the outputs — and the caller reads image.psnr(), image.accuracy() and, when wanted, image.image()."""
     import collections
     import functools
     import operator
     rec = train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_collisions, batch_percentage=batch_percentage,
                       should_shuffle=should_shuffle, shuffled_indices=shuffled_indices, previous_collisions=previous_collisions,
                       previous_min_possible_collisions=previous_min_possible_collisions, should_calc_counts=should_calc_counts,
-                      graph=graph)
+                      graph=graph, image=image)
     hash_mode = bool(models.should_use_hash_function)
     loss_item = float(torch.stack(rec["loss"]).double().mean().item())            # np.mean over batches (functions.py:286)
     mse_loss = float(torch.stack(rec["mse"]).double().mean().item())
@@ -837,13 +846,13 @@ def train_step(net, loss_fn, optimizer, x, target, w, h, hash_table_size, topk_k
     kl_div_losses = None if no_dist else torch.stack(rec["kls"]).double().mean(0).cpu().numpy()
     collisions_losses = None if no_dist else torch.stack(rec["colls"]).double().mean(0).cpu().numpy()
     outputs, indices = rec["outputs"], rec["indices"]
-    if should_shuffle:
+    if should_shuffle and (image is None or indices is not None):
         ro = reordered_indices
         if ro is None:                                  # inverse permutation (main.py:55-58)
             ro = torch.empty_like(shuffled_indices)
             ro[shuffled_indices.long()] = torch.arange(shuffled_indices.numel(), device=shuffled_indices.device, dtype=ro.dtype)
         ro = ro.long().to(outputs.device)
-        outputs = outputs[ro]
+        outputs = outputs[ro] if image is None else None
         indices = indices[ro] if indices is not None else None
     indices_per_level = []
     if should_calc_counts and indices is not None:
@@ -855,7 +864,9 @@ def train_step(net, loss_fn, optimizer, x, target, w, h, hash_table_size, topk_k
         collisions, min_possible_collisions = rec["collisions"]
     else:
         collisions, min_possible_collisions = torch.tensor([]), torch.tensor([])
-    to_show_img = (outputs * 255).reshape((h, w, 3) if not should_bw else (h, w)).int().detach().cpu().numpy()
+    to_show_img = None
+    if image is None:
+        to_show_img = (outputs * 255).reshape((h, w, 3) if not should_bw else (h, w)).int().detach().cpu().numpy()
     counts_per_level = [
         dict(functools.reduce(operator.add, map(collections.Counter, [c[i] for c in rec["counts"]])))
         for i in range(num_levels) if should_calc_counts
@@ -868,3 +879,84 @@ def calc_psnr(pred: np.ndarray, target: np.ndarray) -> float:
     """reference functions.py:134-136 (peak = max(target))."""
     mse = np.square(pred - target).mean()
     return 20 * np.log10(np.max(target)) - 10 * np.log10(mse)
+
+
+def calc_accuracy(predicted: np.ndarray, target: np.ndarray, size: int) -> float:
+    """reference functions.py:130-131: the share of equal elements, in percent."""
+    return (np.equal(predicted, target).sum() / size) * 100
+
+
+def psnr_from_sums(sse, n, peak_term):
+    """calc_psnr from the integer sum of squared differences over n elements: peak_term = 20 * np.log10(np.max(target)) as
+    numpy evaluates it on the caller's array (a float16 for a uint8 image), the mean formed in float64 as np.mean does.  inf
+    at sse == 0, as numpy gives."""
+    with np.errstate(divide="ignore"):
+        return peak_term - 10 * np.log10(np.float64(sse) / n)
+
+
+class EpochImage:
+    """The epoch's image and its two statistics on the device (reference functions.py:308, 332-335, 690-692): begin() once
+    per epoch, add(out, lo) per batch, then accuracy() / psnr() read 16 bytes; image() is the only bulk copy, on demand.
+    og_image: the array the caller would hand to calc_psnr, (h,w,3) or (h,w), whole values 0..255.  shuffled_indices: the
+    epoch's permutation (batch row lo + i is pixel shuffled_indices[lo + i]); None: batches are consecutive pixels."""
+
+    def __init__(self, og_image, shuffled_indices=None, device="cuda"):
+        og = np.asarray(og_image)
+        if og.ndim not in (2, 3) or og.size == 0 or (og.ndim == 3 and not 1 <= og.shape[2] <= 4):
+            raise ValueError(f"og_image must be (h,w) or (h,w,C) with C <= 4, got {og.shape}")
+        self.h, self.w = int(og.shape[0]), int(og.shape[1])
+        self.C = 1 if og.ndim == 2 else int(og.shape[2])
+        self.shape = tuple(og.shape)
+        self.P = self.h * self.w
+        self.n_elems = self.P * self.C
+        t8 = og.astype(np.uint8)
+        if not np.array_equal(t8, og):
+            raise ValueError("og_image must hold whole values in 0..255")
+        # exactly calc_psnr's expression on the array as passed: numpy rounds it to float16 for a uint8 image, and every PSNR
+        # computed by calc_psnr carries that rounding
+        self.peak_term = 20 * np.log10(np.max(og_image))
+        dev = torch.device(device)
+        self.perm = None
+        if shuffled_indices is not None:
+            perm = torch.as_tensor(shuffled_indices).reshape(-1)
+            if perm.numel() != self.P or perm.dtype.is_floating_point:
+                raise ValueError(f"shuffled_indices must be {self.P} integers")
+            if int(perm.min()) < 0 or int(perm.max()) >= self.P:      # the kernel trusts it: a bad index would be a stray write
+                raise ValueError(f"shuffled_indices must lie in [0, {self.P})")
+            self.perm = perm.to(device=dev, dtype=torch.int32).contiguous()
+        self.target = torch.from_numpy(np.ascontiguousarray(t8).reshape(-1)).to(dev)
+        self.img = torch.zeros((self.P, self.C), dtype=torch.int32, device=dev)
+        self._sums = torch.zeros((2,), dtype=torch.int64, device=dev)
+        self._workspace = ops.image_metrics_workspace(self.n_elems, dev)
+
+    def begin(self):
+        """zeroes the image: pixels no batch visits stay 0, as in train_epoch's outputs buffer"""
+        self.img.zero_()
+
+    def add(self, out, lo):
+        """one batch's decoder output (n,C) fp32 contiguous, whose first row is batch-order row lo of the epoch"""
+        if out.dim() != 2 or out.shape[1] != self.C:
+            raise ValueError(f"out must be (n, {self.C}), got {tuple(out.shape)}")
+        if lo < 0 or lo + out.shape[0] > self.P:
+            raise ValueError(f"rows [{lo}, {lo + out.shape[0]}) leave the image's {self.P} pixels")
+        ops.image_scatter(out, self.perm, self.img, lo)
+
+    def sums(self):
+        """device int64 pair (#equal elements, sum of squared differences); no synchronisation.  Integers: a data-parallel
+        caller can all-reduce them."""
+        return ops.image_metrics(self.img, self.target, self._sums, self._workspace)
+
+    def accuracy(self):
+        eq = self.sums().cpu().numpy()[0]
+        return float((eq / self.n_elems) * 100)
+
+    def psnr(self):
+        sse = self.sums().cpu().numpy()[1]
+        return float(psnr_from_sums(sse, self.n_elems, self.peak_term))
+
+    def image_tensor(self):
+        """device int32 (h,w,C) / (h,w) view of the image"""
+        return self.img.view(self.shape)
+
+    def image(self):
+        return self.image_tensor().cpu().numpy()

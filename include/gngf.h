@@ -474,6 +474,20 @@ int gngf_adam_step_masked(const void* segments, int nseg, int64_t total_blocks, 
                           const float* weight_decay, int ngroups, float beta1, float beta2, float eps, float inv_grad_scale,
                           const void* seg_masks, void* stream);
 
+/* ---- epoch image and its statistics (functions.py:308, 332-335, 690-692) --------------------------------------------
+ * img (P,C) int32 in image order: row perm[lo + i] (perm == NULL: row lo + i), i in [0, n), = (int32)(out[i, :] * 255.0f)
+ * for one batch's outputs out (n,C) fp32 contiguous — one fp32 product, conversion toward zero, no clamp: torch's
+ * (output * 255).int().  C in 1..4, 0 <= lo, lo + n <= P, n > 0.  perm (P) int32: every value must lie in [0, P); the
+ * kernel does not check it (the caller validates the permutation once). */
+int gngf_image_scatter(const float* out, const int32_t* perm, int32_t* img, int64_t lo, int64_t n, int64_t P, int C, void* stream);
+/* sums[0] = #{e : img[e] == target[e]}, sums[1] = sum_e (img[e] - target[e])^2 over n_elems elements: int64 from the first
+ * addition, exact and independent of the launch geometry (per-workgroup partials, one finishing workgroup).
+ * workspace: gngf_image_metrics_workspace_words(n_elems) int64 words, no clearing needed; the partial kernel runs
+ * gngf_image_metrics_blocks(n_elems) workgroups. */
+int gngf_image_metrics_blocks(int64_t n_elems);
+int gngf_image_metrics_workspace_words(int64_t n_elems);
+int gngf_image_metrics(const int32_t* img, const uint8_t* target, int64_t* sums, int64_t* workspace, int64_t n_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,87 @@
+"""CPU: the host half of the device epoch image (train.EpochImage) — PSNR from the integer sum of squared differences
+equals the reference's calc_psnr bit for bit, whatever dtype the target array has (numpy's peak term is a float16 for a
+uint8 image and that rounding must be carried through); calc_accuracy restates functions.py:130-131; the bindings list
+the new entry points."""
+import numpy as np
+import pytest
+
+SHAPES = [(1, 1, 3), (7, 5, 1), (61, 67, 3), (256, 257, 3)]
+
+
+def _pair(shape, dtype, seed):
+    rng = np.random.default_rng(seed)
+    target = rng.integers(0, 256, size=shape).astype(dtype)
+    pred = rng.integers(0, 256, size=shape).astype(np.int32)
+    if pred.size > 1:                                   # a share of exact hits, as a trained model gives
+        hit = rng.random(shape) < 0.3
+        pred[hit] = target[hit].astype(np.int32)
+    if np.array_equal(pred, target):                    # (1,1,3): keep the images different
+        pred.flat[0] = (int(target.flat[0]) + 7) % 256
+    return pred, target
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.int32, np.float64])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_psnr_from_sums_equals_calc_psnr_exactly(shape, dtype):
+    from collision_handling_in_instantngp_amd import train
+    pred, target = _pair(shape, dtype, seed=sum(shape))
+    sse = int(np.square(pred.astype(np.int64) - target.astype(np.int64)).sum())
+    peak_term = 20 * np.log10(np.max(target))
+    if dtype is np.uint8:
+        assert peak_term.dtype == np.float16            # the rounding every golden PSNR carries
+    got = train.psnr_from_sums(sse, pred.size, peak_term)
+    want = train.calc_psnr(pred, target)
+    assert np.isfinite(want)
+    assert got == want, (got, want)
+    assert float(got) == float(want)
+
+
+def test_psnr_from_sums_is_inf_for_identical_images():
+    from collision_handling_in_instantngp_amd import train
+    target = np.arange(60, dtype=np.uint8).reshape(4, 5, 3) + 3
+    with np.errstate(divide="ignore"):
+        want = train.calc_psnr(target.astype(np.int32), target)
+    got = train.psnr_from_sums(0, target.size, 20 * np.log10(np.max(target)))
+    assert got == want == np.inf
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_calc_accuracy_is_the_reference_formula(shape):
+    from collision_handling_in_instantngp_amd import train
+    pred, target = _pair(shape, np.uint8, seed=3 + sum(shape))
+    size = pred.size
+    want = (np.equal(pred, target).sum() / size) * 100          # functions.py:131
+    got = train.calc_accuracy(pred, target, size)
+    assert got == want
+    assert 0.0 <= got < 100.0
+    assert train.calc_accuracy(target.astype(np.int32), target, size) == 100.0
+    eq = int((pred == target).sum())
+    assert got == (np.int64(eq) / size) * 100                   # what EpochImage.accuracy() forms from the device count
+
+
+def test_new_entry_points_are_bound_and_abi_version_stays():
+    from collision_handling_in_instantngp_amd import _lib
+    for name in ("gngf_image_scatter", "gngf_image_metrics", "gngf_image_metrics_blocks", "gngf_image_metrics_workspace_words"):
+        assert name in _lib.SIGNATURES, name
+    assert _lib.ABI_VERSION == 14
+    lib = _lib.load()
+    assert lib.gngf_abi_version() == 14
+    # the size queries launch nothing: one workgroup at least, two words per workgroup, a bounded number of workgroups
+    for n in (1, 3, 4095, 4096, 4097, 3 * 2 ** 20, 2 ** 33):
+        b = lib.gngf_image_metrics_blocks(n)
+        assert 1 <= b <= 1024
+        assert lib.gngf_image_metrics_workspace_words(n) == 2 * b
+    assert lib.gngf_image_metrics_blocks(3 * 2 ** 20) > 256            # the headline image fills the chip
+
+
+def test_cpu_tensors_raise_no_fallback():
+    import torch
+    from collision_handling_in_instantngp_amd import _lib, data, ops
+    img = torch.zeros((4, 3), dtype=torch.int32)
+    with pytest.raises(_lib.GngfLibraryError):
+        ops.image_scatter(torch.zeros((4, 3)), None, img, 0)
+    with pytest.raises(_lib.GngfLibraryError):
+        ops.image_metrics(img, torch.zeros(12, dtype=torch.uint8), torch.zeros(2, dtype=torch.int64),
+                          torch.zeros(2, dtype=torch.int64))
+    with pytest.raises(_lib.GngfLibraryError):
+        data.reassemble_image_device(torch.zeros((4, 3)), torch.arange(4), 2, 2)
