@@ -16,6 +16,7 @@ _P = _c.c_void_p
 _I = _c.c_int
 _L = _c.c_int64
 _F = _c.c_float
+_D = _c.c_double
 
 # name -> argtypes (all return int = hipError_t).  Must mirror include/gngf.h exactly.
 SIGNATURES = {
@@ -95,6 +96,11 @@ SIGNATURES = {
     "gngf_image_metrics_blocks": [_L],
     "gngf_image_metrics_workspace_words": [_L],
     "gngf_image_metrics": [_P, _P, _P, _P, _L, _P],
+    "gngf_epoch_state_bytes": [],
+    "gngf_epoch_log_int_columns": [_I, _I],
+    "gngf_epoch_tail": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _D, _D, _I, _L, _P],
+    "gngf_snapshot_block_bytes": [],
+    "gngf_snapshot_if": [_P, _I, _L, _P, _P],
 }
 
 ABI_VERSION = 14

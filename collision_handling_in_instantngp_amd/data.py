@@ -8,6 +8,7 @@ written against it finds the same names and conventions:
   reassemble_image_device                  the same image as a device tensor, written by the scatter kernel
   save_checkpoint / load_checkpoint        functions.py:761-781, models.py HPD/encoding weight paths: the five
                                            state-dict files of the reference, loadable in either direction
+  save_snapshot                            the same five files from the best state train.fit kept on the device
 
 Host-side numpy/torch only, with one exception: reassemble_image_device runs the image scatter kernel (csrc/metrics.hip,
 through ops.image_scatter) and needs device tensors."""
@@ -139,6 +140,31 @@ def save_checkpoint(net, optimizer, folder: str) -> dict:
     if getattr(net, "HPD", None) is not None:
         torch.save(net.HPD.state_dict(), paths["HPD"])
     torch.save(net.mlp.state_dict(), paths["mlp"])
+    return paths
+
+
+def save_snapshot(snapshot, net, optimizer, folder: str) -> dict:
+    """save_checkpoint's five files from a train.DeviceSnapshot of train.state_tensors(net, optimizer) — the best state
+    fit() kept on the device — instead of the live model: same names and layouts, loadable with load_checkpoint.  net and
+    optimizer give the structure (keys, parameter groups, hyper-parameters); every tensor comes from the snapshot."""
+    held = snapshot.tensors()
+    model = {k: held[f"model.{k}"].detach().clone() for k in net.state_dict().keys()}
+
+    def part(prefix):
+        return {k[len(prefix):]: v for k, v in model.items() if k.startswith(prefix)}
+
+    os.makedirs(folder, exist_ok=True)
+    paths = {k: os.path.join(folder, v) for k, v in CHECKPOINT_FILES.items()}
+    torch.save(model, paths["model"])
+    if optimizer is not None:
+        sd = optimizer.state_dict()
+        sd["state"] = {i: {k: (held[f"optimizer.{i}.{k}"].detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
+                       for i, st in sd["state"].items()}
+        torch.save(sd, paths["optimizer"])
+    torch.save(part("encoding."), paths["encoding"])
+    if getattr(net, "HPD", None) is not None:
+        torch.save(part("HPD."), paths["HPD"])
+    torch.save(part("mlp."), paths["mlp"])
     return paths
 
 

@@ -601,15 +601,24 @@ class GeneralNeuralGaugeFields(nn.Module):
              ptr(vert_idx, torch.int32), K, self._hash_table_size, int(vstride), int(NV), ptr(touched), ptr(bitmap), stream_ptr())
 
     @torch.no_grad()
-    def tracked_hash_collisions(self):
-        """(collisions, min_possible_collisions) over every batch seen since start_collision_tracking() — equal to
-        calc_hash_collisions(torch.cat(their index tensors)) (reference models.py:568-619, called at functions.py:327)."""
+    def tracked_slot_counts(self):
+        """(K | 1, L) int32 on the device: distinct slots per (top-K rank, level) over every batch seen since
+        start_collision_tracking() — what the collision statistic is formed from; no synchronisation."""
         from ._lib import call, ptr, stream_ptr
         if self._slot_maps is None:
-            raise RuntimeError("tracked_hash_collisions(): call start_collision_tracking() before the epoch's forward passes")
+            raise RuntimeError("tracked_slot_counts(): call start_collision_tracking() before the epoch's forward passes")
         L, T = self._num_levels, self._hash_table_size
         K = 1 if self._hash_mode else self._topk_k
         bitmap = self._slot_maps[0]
         used = torch.empty((K, L), dtype=torch.int32, device=bitmap.device)
         call("gngf_count_slot_bits", ptr(bitmap), L, K, T, ptr(used), stream_ptr())
-        return self._collisions_from_used(used, bitmap.device)
+        return used
+
+    @torch.no_grad()
+    def tracked_hash_collisions(self):
+        """(collisions, min_possible_collisions) over every batch seen since start_collision_tracking() — equal to
+        calc_hash_collisions(torch.cat(their index tensors)) (reference models.py:568-619, called at functions.py:327)."""
+        if self._slot_maps is None:
+            raise RuntimeError("tracked_hash_collisions(): call start_collision_tracking() before the epoch's forward passes")
+        used = self.tracked_slot_counts()
+        return self._collisions_from_used(used, used.device)

@@ -1850,6 +1850,41 @@ def image_metrics(img, target, sums, workspace):
     return sums
 
 
+def epoch_tail(state, logf, logi, loss, mse, kls, colls, sums, used, nverts, *, hash_source, tolerance, min_delta,
+               should_reset, epochs):
+    """One epoch's decisions on the device (csrc/epoch.hip: gngf_epoch_tail; include/gngf.h has the layouts).  state: the
+    128-byte record (uint8); logf (epochs, 2 + 2 L) float64, logi (epochs, 6 + Kc L) int64: row `state.epoch` is written;
+    loss, mse (nb) and kls, colls (nb, L) | None fp32 per-batch values; sums int64[2]; used (Kc, L) int32 | None; nverts (L)
+    int64.  No synchronisation."""
+    nb, L = loss.numel(), nverts.numel()
+    Kc = 0 if used is None else used.shape[0]
+    if state.dtype != torch.uint8 or state.numel() != query("gngf_epoch_state_bytes"):
+        raise ValueError("state must be the gngf_epoch_state_bytes() record as uint8")
+    if nb < 1 or mse.numel() != nb or sums.numel() != 2:
+        raise ValueError("loss and mse hold one value per batch (at least one), sums two words")
+    for name, t in (("kls", kls), ("colls", colls)):
+        if t is not None and tuple(t.shape) != (nb, L):
+            raise ValueError(f"{name} must be (nb, L) = ({nb}, {L}), got {tuple(t.shape)}")
+    if used is not None and (used.dim() != 2 or used.shape[1] != L or (hash_source and Kc != 1)):
+        raise ValueError(f"used must be (Kc, L) with L = {L} (Kc = 1 for the hash source), got {tuple(used.shape)}")
+    if tuple(logf.shape) != (epochs, 2 + 2 * L) or tuple(logi.shape) != (epochs, query("gngf_epoch_log_int_columns", Kc, L)):
+        raise ValueError("logf must be (epochs, 2 + 2 L) and logi (epochs, 6 + Kc L)")
+    call("gngf_epoch_tail", ptr(state, torch.uint8, "state"), ptr(logf, torch.float64, "logf"), ptr(logi, _i64, "logi"),
+         ptr(loss, _f32, "loss"), ptr(mse, _f32, "mse"), ptr(kls, _f32, "kls"), ptr(colls, _f32, "colls"), nb, L,
+         ptr(sums, _i64, "sums"), ptr(used, _i32, "used"), Kc, int(bool(hash_source)), ptr(nverts, _i64, "nverts"),
+         float(tolerance), float(min_delta), int(bool(should_reset)), int(epochs), stream_ptr())
+
+
+def snapshot_if(table, nrec, total_blocks, flag):
+    """dst = src for the nrec records {src, dst, bytes, first_block} of the device table when the device int32 `flag` is
+    non-zero (csrc/epoch.hip: gngf_snapshot_if); train.DeviceSnapshot packs the table."""
+    if flag.numel() != 1:
+        raise ValueError("flag is one device int32")
+    if nrec == 0:
+        return
+    call("gngf_snapshot_if", ptr(table, torch.uint8, "table"), int(nrec), int(total_blocks), ptr(flag, _i32, "flag"), stream_ptr())
+
+
 # Keep the decoder's activated hidden layers (512 B / pixel) from forward to backward instead of recomputing them: the
 # stores and loads ride under the MFMAs of kernels that leave most of the HBM bandwidth unused (decoder backward 345 -> ~230 us
 # at 2^20 px).  False: recompute (no extra memory).

@@ -724,12 +724,14 @@ class GraphedStep:
 
 def train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_collisions, batch_percentage=1.0,
                 should_shuffle=True, shuffled_indices=None, previous_collisions=None, previous_min_possible_collisions=None,
-                should_calc_counts=False, graph=False, image=None):
+                should_calc_counts=False, graph=False, image=None, slot_counts=False):
     """The batch loop of the reference's train_step (functions.py:183-281): ceil(1/batch_percentage) mini-batches of
     zero_grad -> net -> Loss -> weighted sum -> backward -> step.  graph=True replays each step from a hipGraph
     (GraphedStep, cached on the net per batch shape).  Returns a dict of per-batch device tensors and the outputs /
     indices in batch order; nothing is read back to the host inside the loop.  image: an EpochImage that receives every
-    batch's outputs (one launch after the step, outside any graph) — the epoch's image, accuracy and PSNR on the device."""
+    batch's outputs (one launch after the step, outside any graph) — the epoch's image, accuracy and PSNR on the device.
+    slot_counts: when the forward passes track the slots they use, rec["used"] is the device (K | 1, L) int32 count of distinct
+    slots (net.tracked_slot_counts()) and rec["collisions"], which needs a host read in hash mode, is not formed."""
     net.train()
     shape = w * h
     if image is not None:
@@ -813,7 +815,10 @@ def train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_coll
         rec["counts"].append(counts)
     rec["outputs"], rec["indices"] = outputs, indices
     if tracked:
-        rec["collisions"] = net.tracked_hash_collisions()
+        if slot_counts:
+            rec["used"] = net.tracked_slot_counts()
+        else:
+            rec["collisions"] = net.tracked_hash_collisions()
         net.stop_collision_tracking()
     return rec
 
@@ -960,3 +965,310 @@ class EpochImage:
 
     def image(self):
         return self.image_tensor().cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The epoch loop (reference functions.py:639-814): early stopping, the zero-collision stop, keeping the best model.
+
+class EarlyStopping:
+    """reference utils.py:177-205, branch for branch (quirks included: an equal loss resets the counter, should_reset=False
+    never moves best_loss, a NaN loss becomes best_loss and then every call resets)."""
+
+    def __init__(self, tolerance: int = 5, min_delta: int = 0, should_reset: bool = True):
+        self.tolerance = tolerance
+        self.min_delta = min_delta
+        self.best_loss = np.inf
+        self.counter = 0
+        self.early_stop = False
+        self._should_reset = should_reset
+
+    def __call__(self, loss):
+        if abs(self.best_loss - loss) < self.min_delta and (loss < self.best_loss):
+            self.counter += 1
+        elif abs(self.best_loss - loss) > self.min_delta and (loss > self.best_loss):
+            self.counter += 1
+        else:
+            if not self._should_reset:
+                if self.counter <= 0:
+                    self.counter = 0
+                else:
+                    self.counter -= 1
+            else:
+                self.counter = 0
+                self.best_loss = loss
+        if self.counter >= self.tolerance:
+            self.early_stop = True
+
+
+# csrc/epoch.hip: EpochState (128 bytes)
+EPOCH_STATE = np.dtype([("take", "<i4"), ("last", "<i4"), ("finished", "<i4"), ("stop", "<i4"), ("reason", "<i4"), ("cause", "<i4"),
+                        ("zero_checks", "<i4"), ("zero_all", "<i4"), ("epoch", "<i8"), ("counter", "<i8"), ("best_sse", "<i8"),
+                        ("best_epoch", "<i8"), ("last_epoch", "<i8"), ("best_loss", "<f8"), ("reserved", "<i8", (6,))])
+STOP_REASONS = {0: None, 1: "epochs", 2: "early_stopping", 3: "zero_collisions"}
+# the integer save rule (sse <= best_sse) is the reference's float rule (train_psnr >= best_psnr) while adjacent sums give
+# distinct PSNRs: shown for sse <= 2^44 in DESIGN.md §3 (at 2^50 about one adjacent pair in five rounds to the same PSNR)
+SSE_ORDER_LIMIT = 1 << 44
+
+
+def sse_limit0(n, peak_term):
+    """The largest integer sse with psnr_from_sums(sse, n, peak_term) >= 0 — the reference's `best_psnr = 0` start
+    (functions.py:650) as a bound on the sum of squared differences; -1 when not even sse = 0 qualifies.  Bisection with
+    psnr_from_sums itself, which does not increase with sse."""
+    def ok(s):
+        return bool(psnr_from_sums(s, n, peak_term) >= 0)
+    if not ok(0):
+        return -1
+    lo, hi = 0, 1 << 62                      # ok(lo), not ok(hi)
+    if ok(hi):
+        return hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if ok(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def new_epoch_state(best_sse0):
+    """the state record gngf_epoch_tail starts from, as a numpy record"""
+    st = np.zeros((), dtype=EPOCH_STATE)
+    st["zero_all"] = 1
+    st["best_sse"] = best_sse0
+    st["best_epoch"] = st["last_epoch"] = -1
+    st["best_loss"] = np.inf
+    return st
+
+
+def levels_free_of_collisions(used, nverts, hash_source):
+    """The check of functions.py:684 on the distinct-slot counts used (Kc, L): are the last two levels (the one level when
+    L = 1) free of collisions?  Hash source: nverts - used == 0; GNGF: mean over k clamped at 0 equals 0, i.e. the integer
+    sum over k is <= 0 (models.py:597-607)."""
+    used = np.asarray(used, dtype=np.int64).reshape(-1, len(nverts))
+    diff = np.asarray(nverts, dtype=np.int64)[None, :] - used
+    last2 = diff[:, -2:]
+    return bool((last2[0] == 0).all()) if hash_source else bool((last2.sum(0) <= 0).all())
+
+
+def replay_epoch_decisions(losses, sses, zeros, *, epochs, tolerance, min_delta, should_reset=True, sse_limit):
+    """The decisions of the reference's epoch loop (functions.py:650, 681-688, 761-801) on the host, from the per-epoch
+    train_loss, the image's sse and — zeros, or None when the rule is off — whether the last two levels were free of
+    collisions.  What gngf_epoch_tail computes on the device; tests hold both to the reference's recorded runs."""
+    stopper = EarlyStopping(tolerance=tolerance, min_delta=min_delta, should_reset=should_reset)
+    best_sse, best_epoch, last_epoch, reason, cause = int(sse_limit), -1, -1, None, 0
+    checks = []
+    saved, fired, zero_stop, counter = [], [], [], []
+    for e in range(min(int(epochs), len(losses))):
+        zs = False
+        if zeros is not None and e != 0 and len(checks) < 10:
+            checks.append(bool(zeros[e]))
+            if len(checks) == 10 and all(checks):
+                zs = True
+                stopper.early_stop = True
+                cause = cause or 3
+        take = int(sses[e]) <= best_sse
+        if take:
+            best_sse, best_epoch = int(sses[e]), e
+        f = False
+        if stopper.early_stop:
+            last_epoch, reason = e, STOP_REASONS[cause]
+        else:
+            if e != 0:
+                stopper(losses[e])
+                f = bool(stopper.early_stop)
+                if f:
+                    cause = cause or 2
+            if e == epochs - 1:
+                last_epoch, reason = e, "epochs"
+        saved.append(take), fired.append(f), zero_stop.append(zs), counter.append(int(stopper.counter))
+        if last_epoch >= 0:
+            break
+    return {"saved": saved, "fired": fired, "zero_stop": zero_stop, "counter": counter, "best_epoch": best_epoch,
+            "last_epoch": last_epoch, "stop_reason": reason, "epochs_run": len(saved)}
+
+
+def state_tensors(net, optimizer=None):
+    """name -> tensor of everything a checkpoint holds: 'model.<key>' for every entry of net.state_dict() (BatchNorm buffers
+    included) and 'optimizer.<i>.<key>' for every tensor of the state of the optimizer's i-th parameter (exp_avg, exp_avg_sq,
+    master, step; i counts through the parameter groups as optimizer.state_dict() does)."""
+    out = {f"model.{k}": v for k, v in net.state_dict().items()}
+    if optimizer is not None:
+        i = 0
+        for group in optimizer.param_groups:
+            for p in group["params"]:
+                for k, v in optimizer.state.get(p, {}).items():
+                    if torch.is_tensor(v):
+                        out[f"optimizer.{i}.{k}"] = v
+                i += 1
+    return out
+
+
+class DeviceSnapshot:
+    """Shadows of a set of device tensors and a predicated copy into them: take_if(flag) copies every tensor when the device
+    int32 `flag` is non-zero (one launch of gngf_snapshot_if, no synchronisation), restore() copies the shadows back,
+    tensors() hands them out by name.  "Save the best model" without a file: tensors = state_tensors(net, optimizer), built
+    once the optimizer's state exists.  Tensors that share memory (FusedAdam's one step counter) share their shadow."""
+
+    _RECORD = np.dtype([("src", "<u8"), ("dst", "<u8"), ("bytes", "<i8"), ("first", "<i8")])      # csrc/epoch.hip: SnapshotRecord
+
+    @classmethod
+    def pack_records(cls, pairs, block_bytes):
+        """Pure numpy: (table bytes, records, blocks) for pairs of (src pointer, dst pointer, bytes); pairs of 0 bytes
+        are left out, first_block is the running sum of ceil(bytes / block_bytes)."""
+        pairs = [(int(s), int(d), int(n)) for s, d, n in pairs if int(n) > 0]
+        rec = np.zeros(len(pairs), dtype=cls._RECORD)
+        total_blocks = 0
+        for i, (s, d, n) in enumerate(pairs):
+            rec[i] = (s, d, n, total_blocks)
+            total_blocks += -(-n // block_bytes)
+        return rec.view(np.uint8).reshape(-1), len(pairs), total_blocks
+
+    def __init__(self, tensors):
+        from ._lib import query
+        named = dict(tensors) if isinstance(tensors, dict) else {i: t for i, t in enumerate(tensors)}
+        for name, t in named.items():
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise ValueError(f"DeviceSnapshot: {name!r} does not live on the device — a snapshot is a device-to-device copy. "
+                                 "A torch.optim.Adam that is not capturable keeps its step counter on the host: use "
+                                 "train.FusedAdam (get_optimizer's choice on the GPU), whose whole state is on the device")
+            if not t.is_contiguous():
+                raise ValueError(f"DeviceSnapshot: {name!r} is not contiguous")
+        self._live, self._shadow = named, {}          # (the copy tables hold raw pointers: both sides are kept alive here)
+        by_memory, pairs = {}, []
+        for name, t in named.items():
+            key = (t.data_ptr(), t.numel() * t.element_size(), t.dtype, tuple(t.shape))
+            if key not in by_memory or t.numel() == 0:
+                by_memory[key] = torch.empty_like(t)
+                pairs.append((t.data_ptr(), by_memory[key].data_ptr(), key[1]))
+            self._shadow[name] = by_memory[key]
+        self.bytes = sum(n for _s, _d, n in pairs)
+        dev = next(iter(named.values())).device if named else torch.device("cuda")
+        block = query("gngf_snapshot_block_bytes")
+        raw, self._nrec, self._blocks = self.pack_records(pairs, block)
+        back, _n, _b = self.pack_records([(d, s, n) for s, d, n in pairs], block)
+        self._take = torch.from_numpy(raw.copy()).to(dev)
+        self._back = torch.from_numpy(back.copy()).to(dev)
+        self._one = torch.ones((1,), dtype=torch.int32, device=dev)
+
+    def take_if(self, flag):
+        ops.snapshot_if(self._take, self._nrec, self._blocks, flag)
+
+    def restore(self):
+        """the live tensors get the shadows' contents back, in place (a raw copy: autograd's version counters do not move)"""
+        ops.snapshot_if(self._back, self._nrec, self._blocks, self._one)
+
+    def tensors(self):
+        return dict(self._shadow)
+
+
+class FitResult:
+    """What fit() returns.  log: per recorded epoch, numpy arrays read from the device once — loss, mse (float64), kls,
+    colls_loss (epochs, L; NaN in hash mode), eq, sse (int64), used (epochs, Kc, L), counter, saved, stopper_fired,
+    zero_stop, and psnr, accuracy derived as EpochImage derives them.  last_epoch: the epoch of the reference's `break` (or
+    epochs - 1); best_epoch: the last epoch whose state was saved (-1: none); stop_reason: 'epochs', 'early_stopping' or
+    'zero_collisions'; best: the DeviceSnapshot of best_epoch; issued: epochs enqueued (past last_epoch when a poll came
+    late); restored: the live state was put back to last_epoch's."""
+
+    def __init__(self, log, last_epoch, best_epoch, stop_reason, best, issued, restored):
+        self.log, self.last_epoch, self.best_epoch, self.stop_reason = log, last_epoch, best_epoch, stop_reason
+        self.best, self.issued, self.restored = best, issued, restored
+
+
+def _refuse_host_state(optimizer):
+    if isinstance(optimizer, FusedAdam):
+        return
+    if not all(bool(g.get("capturable", False)) for g in optimizer.param_groups):
+        raise ValueError("fit() keeps the best and the final state in device snapshots and never waits for the host: an optimizer "
+                         "whose state lives on the host (the step counter of a torch.optim.Adam that is not capturable) cannot take "
+                         "part — use train.FusedAdam (get_optimizer's choice on the GPU)")
+
+
+def fit(net, loss_fn, optimizer, x, target, w, h, og_image, *, epochs, tolerance, min_delta, should_reset=True, l_mse, l_js_kl,
+        l_collisions, batch_percentage=1.0, should_shuffle=True, shuffled_indices=None, graph=True, poll_every=16,
+        exact_final=True, after_epoch=None):
+    """The reference's epoch loop (functions.py:639-814) around train_epoch, with every decision taken on the device: per
+    epoch the steps, the image's sums (EpochImage), one launch of gngf_epoch_tail (early stopping as utils.EarlyStopping,
+    the zero-collision stop of functions.py:681-688, `train_psnr >= best_psnr`) and a predicated copy of the whole state
+    into the `best` snapshot.  The host only enqueues; every poll_every epochs it reads one word (`finished`) — the only
+    synchronisation.  Epochs enqueued after the reference's `break` record nothing; exact_final keeps the state of the last
+    epoch in a second snapshot and puts it back, so that after fit() model and optimizer are the reference's at its break
+    (False: they have taken the extra steps, up to poll_every - 1 epochs).  after_epoch(e): called once the launches of epoch e
+    are enqueued; it must not synchronise if the loop is to stay free of host waits.  should_calc_counts is always False.
+    Single process: a model whose data-parallel exchange is enabled is refused."""
+    dp = getattr(net, "dp", None)
+    if dp is not None and (dp.exchange is not None or dp.world > 1 or dp.zero is not None):
+        raise ValueError("fit() runs in one process: this model's data-parallel exchange is enabled")
+    _refuse_host_state(optimizer)
+    epochs, poll_every = int(epochs), max(1, int(poll_every))
+    if epochs < 1:
+        raise ValueError("epochs must be at least 1")
+    dev = x.device
+    if should_shuffle:
+        shuffled_indices = torch.as_tensor(shuffled_indices).to(dev)
+    image = EpochImage(og_image, shuffled_indices if should_shuffle else None, device=dev)
+    if image.n_elems * 255 ** 2 > SSE_ORDER_LIMIT:
+        raise ValueError(f"fit(): {image.n_elems} image elements — the integer save rule is shown to equal the reference's float "
+                         f"PSNR comparison for n * 255^2 <= 2^44 only (DESIGN.md §3)")
+    hash_mode = bool(models.should_use_hash_function)
+    L = net._num_levels
+    nverts_host = np.asarray(net._level_vertex_counts(), dtype=np.int64)
+    nverts = torch.from_numpy(nverts_host).to(dev)
+    nverts_f = nverts.to(torch.float32)
+    min_possible = torch.from_numpy(np.maximum(nverts_host - net._hash_table_size, 0)).to(dev)
+    state = torch.from_numpy(new_epoch_state(sse_limit0(image.n_elems, image.peak_term)).reshape(1).view(np.uint8).copy()).to(dev)
+    flags = state.view(torch.int32)
+    take, last, finished = flags[0:1], flags[1:2], flags[2:3]
+    polled = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
+    logf = logi = best = final = None
+    Kc = 0
+    pc = pm = None
+    issued = 0
+    for e in range(epochs):
+        rec = train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_collisions, batch_percentage=batch_percentage,
+                          should_shuffle=should_shuffle, shuffled_indices=shuffled_indices, previous_collisions=pc,
+                          previous_min_possible_collisions=pm, should_calc_counts=False, graph=graph, image=image, slot_counts=True)
+        used = rec.get("used")
+        if used is None and rec["indices"] is not None:
+            used = net._distinct_slot_counts(rec["indices"], L, net._hash_table_size)
+        if best is None:
+            # the optimizer's state exists now (the first step has run): the shadows are allocated once, here
+            tensors = state_tensors(net, optimizer)
+            best = DeviceSnapshot(tensors)
+            final = DeviceSnapshot(tensors) if exact_final else None
+            Kc = 0 if used is None else int(used.shape[0])
+            logf = torch.full((epochs, 2 + 2 * L), float("nan"), dtype=torch.float64, device=dev)
+            logi = torch.zeros((epochs, 6 + Kc * L), dtype=torch.int64, device=dev)
+        no_dist = hash_mode or not rec["kls"]
+        ops.epoch_tail(state, logf, logi, torch.stack(rec["loss"]).float(), torch.stack(rec["mse"]).float(),
+                       None if no_dist else torch.stack(rec["kls"]).float(), None if no_dist else torch.stack(rec["colls"]).float(),
+                       image.sums(), used, nverts, hash_source=hash_mode, tolerance=tolerance, min_delta=min_delta,
+                       should_reset=should_reset, epochs=epochs)
+        best.take_if(take)
+        if final is not None:
+            final.take_if(last)
+        if used is not None and not hash_mode:
+            # the next epoch's previous_collisions (functions.py:678-679; models.py:597-607), formed on the device
+            pc = (nverts_f[None, :] - used.to(torch.float32)).mean(0).clamp_min_(0)
+            pm = min_possible
+        issued = e + 1
+        if after_epoch is not None:
+            after_epoch(e)
+        if issued % poll_every == 0 or issued == epochs:
+            polled.copy_(finished, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            if int(polled[0]) != 0:
+                break
+    st = state.cpu().numpy().view(EPOCH_STATE)[0]
+    last_epoch, best_epoch = int(st["last_epoch"]), int(st["best_epoch"])
+    restored = False
+    if issued > last_epoch + 1 and final is not None:
+        final.restore()
+        restored = True
+    n = last_epoch + 1
+    lf, li = logf[:n].cpu().numpy(), logi[:n].cpu().numpy()
+    log = {"loss": lf[:, 0], "mse": lf[:, 1], "kls": lf[:, 2:2 + L], "colls_loss": lf[:, 2 + L:2 + 2 * L], "eq": li[:, 0],
+           "sse": li[:, 1], "counter": li[:, 2], "saved": li[:, 3].astype(bool), "stopper_fired": li[:, 4].astype(bool),
+           "zero_stop": li[:, 5].astype(bool), "used": li[:, 6:].reshape(n, Kc, L)}
+    log["psnr"] = np.array([float(psnr_from_sums(s, image.n_elems, image.peak_term)) for s in log["sse"]], dtype=np.float64)
+    log["accuracy"] = np.array([float((q / image.n_elems) * 100) for q in log["eq"]], dtype=np.float64)
+    return FitResult(log, last_epoch, best_epoch, STOP_REASONS[int(st["reason"])], best, issued, restored)

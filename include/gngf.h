@@ -488,6 +488,39 @@ int gngf_image_metrics_blocks(int64_t n_elems);
 int gngf_image_metrics_workspace_words(int64_t n_elems);
 int gngf_image_metrics(const int32_t* img, const uint8_t* target, int64_t* sums, int64_t* workspace, int64_t n_elems, void* stream);
 
+/* ---- epoch loop (functions.py:639-814: early stopping, the zero-collision stop, keeping the best model) ---------------
+ * gngf_epoch_tail: one launch per epoch, one workgroup; takes the epoch's decisions on the device, advances `state` and
+ * writes row e (the epoch's index, kept in the state) of the two logs.  No host synchronisation.
+ * state: gngf_epoch_state_bytes() (128) bytes, 8-byte aligned:
+ *     { int32 take, last, finished, stop, reason, cause, zero_checks, zero_all;
+ *       int64 epoch, counter, best_sse, best_epoch, last_epoch; double best_loss; int64 reserved[6]; }
+ *   initialised by the host: zeros, zero_all = 1, best_sse = the largest sse whose PSNR is >= 0 (-1: none), best_epoch =
+ *   last_epoch = -1, best_loss = +inf.  take / last: flags for gngf_snapshot_if; finished: set with the last epoch — from
+ *   then on a call changes nothing but take = last = 0.  reason (valid once finished): 1 `epochs` reached, 2 the early
+ *   stopper, 3 the zero-collision rule.
+ * loss, mse (nb) and kls, colls (nb, L; both may be NULL) fp32: per-batch values; their means are sequential sums in batch
+ * order in double, divided by nb (np.mean for nb < 8).  sums: int64[2] of gngf_image_metrics.  used (Kc, L) int32 distinct
+ * slot counts (gngf_count_slot_bits / gngf_distinct_slot_counts) or NULL with Kc = 0: the zero-collision rule is off;
+ * hash_source != 0 (Kc = 1): level l is free of collisions when nverts[l] - used[0,l] == 0, otherwise when
+ * sum_k (nverts[l] - used[k,l]) <= 0 (mean over k, clamped at 0, compared with 0).  nverts (L) int64.
+ * logf (epochs, 2 + 2 L) double: loss, mse, kls[L], colls[L] (NaN where NULL).
+ * logi (epochs, gngf_epoch_log_int_columns(Kc, L) = 6 + Kc L) int64: equal elements, sse, the stopper's counter, saved,
+ * stopper fired, zero-collision stop, used[Kc L].
+ * Order within an epoch: zero-collision rule (epochs 1..10), save decision (sse <= best_sse), break if the stop flag is
+ * set, else for e != 0 EarlyStopping.__call__ (utils.py:186-205). */
+int gngf_epoch_state_bytes(void);
+int gngf_epoch_log_int_columns(int Kc, int L);
+int gngf_epoch_tail(void* state, double* logf, int64_t* logi, const float* loss, const float* mse, const float* kls,
+                    const float* colls, int nb, int L, const int64_t* sums, const int32_t* used, int Kc, int hash_source,
+                    const int64_t* nverts, double tolerance, double min_delta, int should_reset, int64_t epochs, void* stream);
+/* Predicated multi-tensor copy: when *flag != 0, dst = src for every record of the device array
+ *     { const void* src; void* dst; int64_t bytes; int64_t first_block; }   (32 bytes)
+ * with first_block = running sum of ceil(bytes / gngf_snapshot_block_bytes()) and total_blocks that sum (records of 0 bytes
+ * are left out by the packer).  Any dtype: sizes are bytes; 16-byte accesses where both pointers allow, 4-byte or single
+ * bytes elsewhere.  When *flag == 0 every workgroup returns after reading it.  src and dst must not overlap. */
+int gngf_snapshot_block_bytes(void);
+int gngf_snapshot_if(const void* records, int nrec, int64_t total_blocks, const int32_t* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
