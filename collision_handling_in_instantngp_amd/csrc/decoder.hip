@@ -1505,3 +1505,5 @@ extern "C" int gngf_debug_read_stamps(unsigned long long* host16) {
   return (int)hipMemcpyFromSymbol(host16, HIP_SYMBOL(gngf::g_stamps), 16 * sizeof(unsigned long long));
 }
 #endif
+
+#include "render.inc"

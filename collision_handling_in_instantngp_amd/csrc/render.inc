@@ -1,0 +1,360 @@
+// Forward-only render of a pixel lattice in ONE launch (included at the end of decoder.hip: it needs that file's local helpers —
+// stage_raw / raw_offsets, crow / kmapC, the MFMA macro and the 4x4x1 output layer with its sigmoid).
+//
+// decoder_fwd_kernel with its input produced in place: a lane owns one pixel of the lattice (col = lane & 31 of the transposed
+// products), computes the pixel's coordinate from its row and column — ((float)(r0 + r) / denom, (float)(c0 + c) / denom), one
+// correctly rounded fp32 division per axis, no coordinate tensor — and gathers the features of ITS lane half (features
+// h S0 .. h S0 + S0 - 1, feature k of level k / F) straight into xr[], the registers layer 0 reads as its B operands.  Nothing is
+// binned (a lattice is in tile order already), no (P, L F) encoding is written or read, and the launch has no workspace.
+//   workgroup = a 16-column x 8-row block of the lattice, wave = 8 x 4 of it (neighbouring lanes gather from neighbouring
+//   vertices), blocks walked grid-stride by a persistent grid with one wave per SIMD; weights and biases live in registers.
+// The interpolation is encode_fwd_kernel's, operation for operation: make_cell, spatial_hash | vert_idx / vert_w of vertex
+// gy vstride + gx (clamped), the K rows of a vertex accumulated in ascending k, ((f0 c0 + f1 c1) + f2 c2) + f3 c3.
+// Schedule of a block (16 features of the lane half = one gather group; 64-wide inputs have two):
+//   layer 0 | issue group 0 of the NEXT block | layer 1 | combine group 0 -> xr, issue group 1 | layer 2 | combine group 1 | stores
+// Hash source: the loads of a group are in flight under the 64 MFMAs that follow them.  Vertex-table source: the row index
+// depends on a load, so a group's K rows are accumulated where the group is issued (levels in chunks of <= 8 corners, the
+// next k's index / weight pairs requested while the rows of k arrive).
+// Registers: the 32-feature forms fit the 512-entry file; the 64-feature forms (64 more weight registers, two groups) spill
+// 28 - 125 registers to scratch in the gather phases.
+namespace gngf {
+
+constexpr int kRenderCols = 16, kRenderRows = 8;        // the workgroup's block; a wave renders 8 x 4 of it
+
+struct RenderArgs {
+  const void* tables; const int32_t* vert_idx; const float* vert_w; const int32_t* n_ls;
+  const float *W0, *b0, *W1, *b1, *W2, *b2;
+  float* rgb; int32_t* img;
+  int64_t rows, cols, r0, c0;
+  float denom;
+  int L, F;
+  int64_t T;
+  int K, vstride;
+  int64_t NV;
+  int out_dim;
+  bool pow2;
+};
+
+// one table row (F consecutive values, F sizeof(TT)-aligned: the table base is 16-byte aligned) as fp32 — tload's values
+template <int F> __device__ __forceinline__ void row_load(const float* r, float (&o)[F]) {
+  if constexpr (F == 4) { const float4 q = *reinterpret_cast<const float4*>(r); o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w; }
+  else if constexpr (F == 2) { const float2 q = *reinterpret_cast<const float2*>(r); o[0] = q.x; o[1] = q.y; }
+  else o[0] = tload(r);
+}
+template <int F> __device__ __forceinline__ void row_load(const __half* r, float (&o)[F]) {
+  if constexpr (F == 4) {
+    const __half2 q0 = reinterpret_cast<const __half2*>(r)[0], q1 = reinterpret_cast<const __half2*>(r)[1];
+    o[0] = __low2float(q0); o[1] = __high2float(q0); o[2] = __low2float(q1); o[3] = __high2float(q1);
+  } else if constexpr (F == 2) {
+    const __half2 q = *reinterpret_cast<const __half2*>(r); o[0] = __low2float(q); o[1] = __high2float(q);
+  } else o[0] = tload(r);
+}
+
+// 16 features of one lane half: the four corner values of every feature and the scaled coordinate (x N_l, y N_l) of every
+// level, from which the combine forms the four coefficients again (make_cell on a grid of 1: the same operations, the same
+// bits) — two registers a level across the MFMA run instead of four
+struct RenderGroup { float fv[4][16]; float sx[16], sy[16]; };
+__device__ __forceinline__ Cell scaled_cell(float x, float y, int n, float& sx, float& sy) {
+  const float fn = (float)n;
+  sx = x * fn; sy = y * fn;
+  return make_cell(sx, sy, 1);
+}
+
+// Levels lev0 .. lev0 + 16 / F - 1 at coordinate (x, y).  Levels >= L (the narrower forms) give zeros.
+template <int F, bool VT, bool EXACT, typename TT>
+__device__ __forceinline__ void render_issue(RenderGroup& G, const RenderArgs& a, int lev0, float x, float y) {
+  constexpr int NLG = 16 / F;
+  const TT* tables = static_cast<const TT*>(a.tables);
+  if constexpr (!VT) {
+#pragma unroll
+    for (int lv = 0; lv < NLG; ++lv) {
+      const int level = lev0 + lv;
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int f = 0; f < F; ++f) G.fv[v][lv * F + f] = 0.f;
+      G.sx[lv] = G.sy[lv] = 0.f;
+      if (EXACT || level < a.L) {
+        const Cell cell = scaled_cell(x, y, a.n_ls[level], G.sx[lv], G.sy[lv]);
+        const TT* tab = tables + (int64_t)level * a.T * F;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int gx = cell.gx + (v & 1), gy = cell.gy + (v >> 1);
+          float o[F];
+          row_load<F>(tab + spatial_hash(gx, gy, a.T, a.pow2) * F, o);
+#pragma unroll
+          for (int f = 0; f < F; ++f) G.fv[v][lv * F + f] = o[f];
+        }
+      }
+    }
+  } else {
+    constexpr int CL = F == 4 ? 1 : 2;                    // levels per chunk: <= 8 corners (16 row values) in flight
+#pragma unroll
+    for (int ch = 0; ch < NLG / CL; ++ch) {
+      const int levc = lev0 + ch * CL;
+      if (!EXACT && levc >= a.L) {
+#pragma unroll
+        for (int j = 0; j < CL; ++j)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            G.sx[ch * CL + j] = G.sy[ch * CL + j] = 0.f;
+#pragma unroll
+            for (int f = 0; f < F; ++f) G.fv[v][(ch * CL + j) * F + f] = 0.f;
+          }
+        continue;
+      }
+      unsigned vk[CL][4];                                 // vid K (host: NV K < 2^31)
+      const TT* tab[CL];
+      bool on[CL];
+#pragma unroll
+      for (int j = 0; j < CL; ++j) {
+        on[j] = EXACT || levc + j < a.L;
+        const int level = on[j] ? levc + j : 0;           // a level past the end reads level 0 and is zeroed below
+        const Cell cell = scaled_cell(x, y, a.n_ls[level], G.sx[ch * CL + j], G.sy[ch * CL + j]);
+        tab[j] = tables + (int64_t)level * a.T * F;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int gx = cell.gx + (v & 1), gy = cell.gy + (v >> 1);
+          int64_t vid = (int64_t)gy * a.vstride + gx;
+          vid = vid < 0 ? 0 : (vid >= a.NV ? a.NV - 1 : vid);   // never fault on out-of-domain coordinates
+          vk[j][v] = (unsigned)(vid * a.K);
+        }
+      }
+      float acc[CL][4][F], wc[CL][4];
+      int ic[CL][4];
+#pragma unroll
+      for (int j = 0; j < CL; ++j)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          wc[j][v] = a.vert_w[vk[j][v]];
+          ic[j][v] = a.vert_idx[vk[j][v]];
+#pragma unroll
+          for (int f = 0; f < F; ++f) acc[j][v][f] = 0.f;
+        }
+      for (int k = 0; k < a.K; ++k) {
+        float row[CL][4][F], wn[CL][4];
+        int in[CL][4];
+        const unsigned kn = k + 1 < a.K ? k + 1 : k;      // (the last trip asks for its own pair again: no branch)
+#pragma unroll
+        for (int j = 0; j < CL; ++j)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) row_load<F>(tab[j] + (int64_t)ic[j][v] * F, row[j][v]);
+#pragma unroll
+        for (int j = 0; j < CL; ++j)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) { wn[j][v] = a.vert_w[vk[j][v] + kn]; in[j][v] = a.vert_idx[vk[j][v] + kn]; }
+#pragma unroll
+        for (int j = 0; j < CL; ++j)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+#pragma unroll
+            for (int f = 0; f < F; ++f) acc[j][v][f] += row[j][v][f] * wc[j][v];
+            wc[j][v] = wn[j][v]; ic[j][v] = in[j][v];
+          }
+      }
+#pragma unroll
+      for (int j = 0; j < CL; ++j)
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+#pragma unroll
+          for (int f = 0; f < F; ++f) G.fv[v][(ch * CL + j) * F + f] = on[j] ? acc[j][v][f] : 0.f;
+    }
+  }
+}
+
+template <int F, int OFF, int S0>
+__device__ __forceinline__ void render_combine(const RenderGroup& G, float (&xr)[S0]) {
+#pragma unroll
+  for (int lv = 0; lv < 16 / F; ++lv) {
+    const Cell cell = make_cell(G.sx[lv], G.sy[lv], 1);
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+      const int s = lv * F + f;
+      xr[OFF + s] = ((G.fv[0][s] * cell.c[0] + G.fv[1][s] * cell.c[1]) + G.fv[2][s] * cell.c[2]) + G.fv[3][s] * cell.c[3];
+    }
+  }
+}
+
+// hidden_act's values (max(z, 0) | max(z, 0.01 z)) as an expression the compiler schedules itself
+template <bool LEAKY> __device__ __forceinline__ float render_act(float z) { return LEAKY ? fmaxf(z, 0.01f * z) : fmaxf(z, 0.f); }
+
+// F is wave-uniform: one branch per gather phase picks the unrolled form
+#define RENDER_F(...)                                                  \
+  do {                                                                 \
+    if (a.F == 2) { constexpr int kF = 2; __VA_ARGS__; }               \
+    else if (a.F == 4) { constexpr int kF = 4; __VA_ARGS__; }          \
+    else if constexpr (KIN == 32) { constexpr int kF = 1; __VA_ARGS__; } /* (F = 1 at 64 features would be 64 levels) */ \
+  } while (0)
+
+template <int KIN, bool LEAKY, bool EXACT, bool VT, typename TT>
+__global__ void __launch_bounds__(kDecThreads, 1)
+render_kernel(const RenderArgs a) {
+  constexpr int S0 = KIN / 2, NG = S0 / 16;
+  const int in_dim = EXACT ? KIN : a.L * a.F;
+  const int out_dim = a.out_dim;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
+  // register-resident operands, gathered from a coalesced LDS copy of the raw weights (as decoder_fwd_kernel)
+  extern __shared__ float raw[];
+  stage_raw(raw, a.W0, a.b0, a.W1, a.b1, a.W2, a.b2, in_dim, out_dim);
+  const RawOff o = raw_offsets(in_dim);
+  float a0r[2][S0], a1r[2][32], w2a[32];
+  f32x16 b0v[2], b1v[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+#pragma unroll
+    for (int s = 0; s < S0; ++s) { const int k = h * S0 + s; a0r[t][s] = k < in_dim ? raw[o.w0 + (32 * t + i) * (in_dim + 1) + k] : 0.f; }
+#pragma unroll
+    for (int s2 = 0; s2 < 32; ++s2) a1r[t][s2] = raw[o.w1 + (32 * t + i) * 65 + kmapC(s2, h)];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { b0v[t][r] = raw[o.b0 + 32 * t + crow(r, h)]; b1v[t][r] = raw[o.b1 + 32 * t + crow(r, h)]; }
+  }
+  const int ch = lane & 3;
+#pragma unroll
+  for (int s2 = 0; s2 < 32; ++s2) w2a[s2] = raw[o.w2 + ch * 65 + kmapC(s2, h)];
+  float b2v[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) b2v[c] = raw[o.b2 + c];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+#pragma unroll
+    for (int s = 0; s < S0; ++s) asm volatile("" : "+a"(a0r[t][s]));
+#pragma unroll
+    for (int s2 = 0; s2 < 32; ++s2) asm volatile("" : "+a"(a1r[t][s2]));
+  }
+#pragma unroll
+  for (int s2 = 0; s2 < 32; ++s2) asm volatile("" : "+a"(w2a[s2]));
+
+  // blocks of the lattice, row-major; the grid stride is applied to (block row, block column) without a division per block
+  const int64_t nbx = (a.cols + kRenderCols - 1) / kRenderCols, nby = (a.rows + kRenderRows - 1) / kRenderRows;
+  const int64_t nblocks = nbx * nby;
+  const int64_t gq = (int64_t)gridDim.x / nbx, gr = (int64_t)gridDim.x % nbx;
+  int64_t by = (int64_t)blockIdx.x / nbx, bx = (int64_t)blockIdx.x % nbx;
+  const int lr = (wave >> 1) * 4 + (i >> 3), lc = (wave & 1) * 8 + (i & 7);      // this lane's pixel inside a block
+  // (r0 + rows, c0 + cols <= 2^24: the integers are exact in fp32; lanes past the ragged edges compute and store nothing)
+  auto coord = [&](int64_t brow, int64_t bcol, float& x, float& y) {
+    x = (float)(int)(a.r0 + brow * kRenderRows + lr) / a.denom;
+    y = (float)(int)(a.c0 + bcol * kRenderCols + lc) / a.denom;
+  };
+  float xr[S0], x, y;
+  RenderGroup G;
+  coord(by, bx, x, y);
+  RENDER_F(render_issue<kF, VT, EXACT, TT>(G, a, h * (S0 / kF), x, y); render_combine<kF, 0>(G, xr));
+  if constexpr (NG == 2)
+    RENDER_F(render_issue<kF, VT, EXACT, TT>(G, a, h * (S0 / kF) + 16 / kF, x, y); render_combine<kF, 16>(G, xr));
+  for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+    const int64_t pr = by * kRenderRows + lr, pc = bx * kRenderCols + lc;         // this block's pixel
+    int64_t nrow = by + gq, ncol = bx + gr;
+    if (ncol >= nbx) { ncol -= nbx; ++nrow; }
+    if (blk + gridDim.x >= nblocks) { nrow = by; ncol = bx; }                     // past the end: this block again, never used
+    coord(nrow, ncol, x, y);
+    by = nrow; bx = ncol;
+    // MFMA runs and VALU bursts alternate as in decoder_fwd_kernel, but through the MFMA builtin and plain C++ activations: the
+    // gather phases keep the register file full, hipcc moves values between VGPRs and AGPRs around them, and it pads the
+    // hazards of instructions it knows — not those of hand-written MFMA statements (measured: wrong pixels in the narrow and
+    // vertex-table forms with the asm chains of decoder_fwd_kernel)
+    f32x16 acc1[2] = {b0v[0], b0v[1]}, acc2[2] = {b1v[0], b1v[1]};
+#pragma unroll
+    for (int sx = 0; sx < S0; ++sx) {
+      acc1[0] = MFMA(a0r[0][sx], xr[sx], acc1[0]);
+      acc1[1] = MFMA(a0r[1][sx], xr[sx], acc1[1]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    RENDER_F(render_issue<kF, VT, EXACT, TT>(G, a, h * (S0 / kF), x, y));
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc1[t][r] = render_act<LEAKY>(acc1[t][r]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s2 = 0; s2 < 32; ++s2) {
+      const float b = acc1[s2 >> 4][s2 & 15];
+      acc2[0] = MFMA(a1r[0][s2], b, acc2[0]);
+      acc2[1] = MFMA(a1r[1][s2], b, acc2[1]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    RENDER_F(render_combine<kF, 0>(G, xr));
+    if constexpr (NG == 2) RENDER_F(render_issue<kF, VT, EXACT, TT>(G, a, h * (S0 / kF) + 16 / kF, x, y));
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc2[t][r] = render_act<LEAKY>(acc2[t][r]);
+    __builtin_amdgcn_sched_barrier(0);
+    f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s2 = 0; s2 < 32; s2 += 2) {
+      d0 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2a[s2], acc2[s2 >> 4][s2 & 15], d0, 0, 0, 0);
+      d1 = __builtin_amdgcn_mfma_f32_4x4x1f32(w2a[s2 + 1], acc2[(s2 + 1) >> 4][(s2 + 1) & 15], d1, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (NG == 2) RENDER_F(render_combine<kF, 16>(G, xr));
+    {
+      float yv[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float dc = d0[c] + d1[c];
+        const float z = dc + __shfl_xor(dc, 32, 64) + b2v[c];
+        // Sigmoid on the hardware exp2 / rcp units, as decoder_fwd_kernel
+        yv[c] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z * -1.4426950408889634f));
+      }
+      if (h == 0 && pr < a.rows && pc < a.cols) {
+        const int64_t e = (pr * a.cols + pc) * out_dim;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (c < out_dim) {
+            if (a.rgb) a.rgb[e + c] = yv[c];
+            if (a.img) a.img[e + c] = (int32_t)(yv[c] * 255.0f);      // (output * 255).int(): csrc/metrics.hip
+          }
+      }
+    }
+  }
+}
+#undef RENDER_F
+
+using RenderKern = void (*)(const RenderArgs);
+template <int KIN, typename TT> static RenderKern render_pick(bool leaky, bool exact, bool vt) {
+  if (leaky) {
+    if (exact) return vt ? render_kernel<KIN, true, true, true, TT> : render_kernel<KIN, true, true, false, TT>;
+    return vt ? render_kernel<KIN, true, false, true, TT> : render_kernel<KIN, true, false, false, TT>;
+  }
+  if (exact) return vt ? render_kernel<KIN, false, true, true, TT> : render_kernel<KIN, false, true, false, TT>;
+  return vt ? render_kernel<KIN, false, false, true, TT> : render_kernel<KIN, false, false, false, TT>;
+}
+
+}  // namespace gngf
+
+// rgb (rows cols, out_dim) fp32 and / or img (same shape) int32 = (int)(rgb * 255.0f) of the model on the lattice
+// ((r0 + r) / denom, (c0 + c) / denom), r < rows, c < cols, row-major.  See include/gngf.h.
+extern "C" int gngf_render(const void* tables, int feat_dtype, const int32_t* vert_idx, const float* vert_w, const int32_t* n_ls,
+                           const float* W0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
+                           float* rgb, int32_t* img, int64_t rows, int64_t cols, int64_t r0, int64_t c0, float denom,
+                           int L, int F, int64_t T, int K, int mode, int vstride, int64_t NV, int out_dim, int leaky, void* stream) {
+  constexpr int64_t kExact = (int64_t)1 << 24;            // integers up to here are exact in fp32
+  GNGF_CHECK_ARG(L > 0 && L <= GNGF_MAX_LEVELS && (F == 1 || F == 2 || F == 4) && L * F <= 64 && T > 0);
+  GNGF_CHECK_ARG(out_dim > 0 && out_dim <= 4);
+  GNGF_CHECK_ARG(rows >= 1 && cols >= 1 && denom > 0.f && r0 >= -kExact && c0 >= -kExact && r0 + rows <= kExact && c0 + cols <= kExact);
+  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || mode == GNGF_MODE_VERTEX_TABLE);
+  GNGF_CHECK_ARG(feat_dtype == GNGF_FEAT_F32 || feat_dtype == GNGF_FEAT_F16);
+  GNGF_CHECK_ARG(tables && n_ls && W0 && b0 && W1 && b1 && W2 && b2 && (rgb || img));
+  GNGF_CHECK_ARG((reinterpret_cast<uintptr_t>(tables) & 15) == 0);
+  const bool vt = mode == GNGF_MODE_VERTEX_TABLE;
+  if (vt) GNGF_CHECK_ARG(vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0 && NV * K < ((int64_t)1 << 31));
+  RenderArgs a;
+  a.tables = tables; a.vert_idx = vert_idx; a.vert_w = vert_w; a.n_ls = n_ls;
+  a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2;
+  a.rgb = rgb; a.img = img;
+  a.rows = rows; a.cols = cols; a.r0 = r0; a.c0 = c0; a.denom = denom;
+  a.L = L; a.F = F; a.T = T; a.K = vt ? K : 0; a.vstride = vt ? vstride : 0; a.NV = vt ? NV : 0;
+  a.out_dim = out_dim; a.pow2 = (T & (T - 1)) == 0;
+  const int in_dim = L * F;
+  const int64_t nblocks = ((cols + kRenderCols - 1) / kRenderCols) * ((rows + kRenderRows - 1) / kRenderRows);
+  const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);      // one persistent workgroup per CU
+  const size_t smem = sizeof(float) * (size_t)raw_offsets(in_dim).total;
+  const bool f16 = feat_dtype == GNGF_FEAT_F16;
+  RenderKern fn;
+  if (in_dim <= 32) fn = f16 ? render_pick<32, __half>(leaky != 0, in_dim == 32, vt) : render_pick<32, float>(leaky != 0, in_dim == 32, vt);
+  else fn = f16 ? render_pick<64, __half>(leaky != 0, in_dim == 64, vt) : render_pick<64, float>(leaky != 0, in_dim == 64, vt);
+  fn<<<dim3(grid), dim3(kDecThreads), smem, as_stream(stream)>>>(a);
+  GNGF_RETURN_LAUNCH();
+}

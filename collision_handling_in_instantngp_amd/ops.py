@@ -1885,6 +1885,37 @@ def snapshot_if(table, nrec, total_blocks, flag):
     call("gngf_snapshot_if", ptr(table, torch.uint8, "table"), int(nrec), int(total_blocks), ptr(flag, _i32, "flag"), stream_ptr())
 
 
+def render_lattice(tables, n_ls, decoder_params, rows, cols, denom, origin=(0, 0), *, vert_idx=None, vert_w=None, vstride=0,
+                   leaky=False, out_rgb=None, out_image=None):
+    """The model on the lattice ((r0 + r) / denom, (c0 + c) / denom), r < rows, c < cols, in one forward-only launch
+    (csrc/render.inc: gngf_render; include/gngf.h has the contract).  tables (L,T,F) fp32 | fp16, n_ls (L) int32,
+    decoder_params [W0, b0, W1, b1, W2, b2]; vert_idx / vert_w (NV,K) and vstride select the vertex-table source, None the
+    spatial hash.  out_rgb (rows cols, C) fp32 and / or out_image (same shape) int32 are written; at least one is needed.
+    No autograd, no workspace, no allocation, no synchronisation — and no StepConfig: this is not a step of training."""
+    L, T, F = tables.shape
+    W0, b0, W1, b1, W2, b2 = decoder_params
+    C = W2.shape[0]
+    if tuple(W0.shape) != (64, L * F) or tuple(W1.shape) != (64, 64) or W2.shape[1] != 64:
+        raise ValueError(f"render_lattice: decoder ({L * F} -> 64 -> 64 -> C) expected, got {tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
+    if n_ls.numel() != L:
+        raise ValueError(f"n_ls holds {n_ls.numel()} resolutions for {L} levels")
+    if out_rgb is None and out_image is None:
+        raise ValueError("render_lattice: pass out_rgb, out_image or both")
+    for name, t in (("out_rgb", out_rgb), ("out_image", out_image)):
+        if t is not None and t.numel() != rows * cols * C:
+            raise ValueError(f"{name} holds {t.numel()} elements for a {rows} x {cols} x {C} render")
+    tp, code = _tab(tables)
+    vt = vert_idx is not None
+    K = int(vert_idx.shape[1]) if vt else 0
+    NV = int(vert_idx.shape[0]) if vt else 0
+    if vt and tuple(vert_w.shape) != (NV, K):
+        raise ValueError(f"vert_w must be (NV, K) = ({NV}, {K}), got {tuple(vert_w.shape)}")
+    call("gngf_render", tp, code, ptr(vert_idx, _i32, "vert_idx"), ptr(vert_w, _f32, "vert_w"), ptr(n_ls, _i32, "n_ls"),
+         ptr(W0, _f32, "W0"), ptr(b0, _f32, "b0"), ptr(W1, _f32, "W1"), ptr(b1, _f32, "b1"), ptr(W2, _f32, "W2"), ptr(b2, _f32, "b2"),
+         ptr(out_rgb, _f32, "out_rgb"), ptr(out_image, _i32, "out_image"), int(rows), int(cols), int(origin[0]), int(origin[1]),
+         float(denom), L, F, T, K, MODE_VERTEX_TABLE if vt else MODE_HASH, int(vstride), NV, C, int(bool(leaky)), stream_ptr())
+
+
 # Keep the decoder's activated hidden layers (512 B / pixel) from forward to backward instead of recomputing them: the
 # stores and loads ride under the MFMAs of kernels that leave most of the HBM bandwidth unused (decoder backward 345 -> ~230 us
 # at 2^20 px).  False: recompute (no extra memory).

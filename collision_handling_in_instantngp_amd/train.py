@@ -1272,3 +1272,137 @@ def fit(net, loss_fn, optimizer, x, target, w, h, og_image, *, epochs, tolerance
     log["psnr"] = np.array([float(psnr_from_sums(s, image.n_elems, image.peak_term)) for s in log["sse"]], dtype=np.float64)
     log["accuracy"] = np.array([float((q / image.n_elems) * 100) for q in log["eq"]], dtype=np.float64)
     return FitResult(log, last_epoch, best_epoch, STOP_REASONS[int(st["reason"])], best, issued, restored)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Rendering: the picture a model encodes, on any pixel lattice, in one forward-only launch (csrc/render.inc).
+
+LATTICE_EXACT = 1 << 24      # pixel indices up to here are exact in fp32: the kernel forms coordinates from them
+
+
+def _check_lattice(rows, cols, denom, origin):
+    rows, cols, r0, c0 = int(rows), int(cols), int(origin[0]), int(origin[1])
+    if rows < 1 or cols < 1:
+        raise ValueError(f"a lattice has at least one row and one column, got {rows} x {cols}")
+    if not np.float32(denom) > 0:
+        raise ValueError(f"denom must be positive, got {denom}")
+    if min(r0, c0) < -LATTICE_EXACT or r0 + rows > LATTICE_EXACT or c0 + cols > LATTICE_EXACT:
+        raise ValueError(f"pixel indices must lie in [-2^24, 2^24] (exact in float32), got origin {(r0, c0)} and {rows} x {cols}")
+    return rows, cols, r0, c0
+
+
+def lattice_coordinates(rows, cols, denom, origin=(0, 0)):
+    """Host float32 (rows * cols, 2): the (row, col) coordinate of every lattice point, rows outermost —
+    ((origin[0] + r) / denom, (origin[1] + c) / denom), each one float32 division, which is what the render kernel computes
+    per pixel and, for denom = max(w, h) - 1, what data.normalise_coordinates gives for data.pixel_grid.  For callers and
+    tests: render() itself never builds coordinates."""
+    rows, cols, r0, c0 = _check_lattice(rows, cols, denom, origin)
+    d = np.float32(denom)
+    rr = (np.arange(r0, r0 + rows, dtype=np.int64).astype(np.float32) / d).astype(np.float32)
+    cc = (np.arange(c0, c0 + cols, dtype=np.int64).astype(np.float32) / d).astype(np.float32)
+    return np.stack([np.repeat(rr, cols), np.tile(cc, rows)], axis=1)
+
+
+def _render_setup(net, rows, cols, denom, origin):
+    """Validation shared by render(): (rows, cols, r0, c0, denom, C) or ValueError naming net(x) as the general path."""
+    if denom is None:
+        denom = max(int(rows), int(cols)) - 1           # data.normalise_coordinates: the longer side spans [0, 1]
+    rows, cols, r0, c0 = _check_lattice(rows, cols, denom, origin)
+    general = " — evaluate net(x) on explicit coordinates instead"
+    if models.should_batchnorm_data:
+        raise ValueError("render(): should_batchnorm_data normalises coordinates with batch statistics, a lattice has none" + general)
+    widths = [tuple(seq[0].weight.shape) for seq in net.mlp]
+    L, F = net._num_levels, net._feature_dim
+    if len(widths) != 3 or widths[0] != (64, L * F) or widths[1] != (64, 64) or widths[2][1] != 64 or widths[2][0] > 4:
+        raise ValueError(f"render(): the render kernel holds a decoder with hidden widths [64, 64] and at most 4 outputs, this one is "
+                         f"{[w[::-1] for w in widths]}" + general)
+    if L * F > 64:
+        raise ValueError(f"render(): L * F = {L * F} encoder features, the render kernel holds at most 64" + general)
+    if F not in (1, 2, 4):
+        raise ValueError(f"render(): feature_dim = {F}, the render kernel gathers rows of 1, 2 or 4 features" + general)
+    if not net._hash_mode:
+        d = np.float32(denom)
+        hi = max(np.float32(r0 + rows - 1) / d, np.float32(c0 + cols - 1) / d)
+        if r0 < 0 or c0 < 0 or hi > 1:
+            raise ValueError(f"render(): GNGF indexing looks vertices up in the table over [0, 1]^2; this lattice spans "
+                             f"[{r0 / float(d):g}, {float(hi):g}]" + general)
+    return rows, cols, r0, c0, float(np.float32(denom)), widths[2][0]
+
+
+@torch.no_grad()
+def _render_vertex_table(net):
+    """(vert_idx, vert_w, vstride) over the (n_max + 2)^2 vertices of [0, 1]^2 for the CURRENT HPD weights.  A frozen HPD: the
+    model's own cached table (keyed on the parameters' data_ptr / _version, models._frozen_vertex_table).  A trainable HPD is
+    updated through raw pointers (FusedAdam, DeviceSnapshot.restore) that move no version counter, so no key can vouch for a
+    cached table: it is evaluated anew for every render, the same two calls as the cached one."""
+    blend = ops.BLEND_CODES[models.should_softmax_topk_features]
+    if net.hpd_is_frozen():
+        _tv, ti, w, vstride, _NV, _order = net._frozen_vertex_table(blend)
+        return ti, w, vstride
+    vstride = net._n_max + 2
+    tv, ti, _, _ = ops.HpdVertexFunction.apply(vstride * vstride, vstride, net._topk_k, None, False, models.HPD_CHUNK_BYTES, None,
+                                               *net.HPD.flat_params())
+    return ti, ops.BlendFunction.apply(tv, blend), vstride
+
+
+@torch.no_grad()
+def render(net, rows, cols, denom=None, origin=(0, 0), *, rgb=True, image=False, out_rgb=None, out_image=None):
+    """The picture the model encodes NOW, on the lattice ((origin[0] + r) / denom, (origin[1] + c) / denom), r < rows,
+    c < cols: one launch of gngf_render — no coordinate tensor, no binning, no (P, L F) encoding in memory, none of the
+    reference-shaped index / probability outputs.  denom None: max(rows, cols) - 1, the training normalisation
+    (data.normalise_coordinates), so render(net, h, w) is the trained image itself.  An integer upscale by s of an h x w image:
+    rows = (h - 1) s + 1, cols = (w - 1) s + 1, denom = (max(w, h) - 1) s — the original pixels are lattice points.
+    Returns what was asked for: rgb (rows * cols, C) float32, image (rows, cols, C) int32 — (rows, cols) for a should_bw model —
+    = (rgb * 255).int(), or the pair (rgb, image).  out_rgb / out_image: buffers to write instead of new tensors (each
+    implies its output); with every requested output given, a hash-mode or frozen-HPD render allocates nothing and never
+    synchronises, so it may be captured in a graph.  GNGF indexing reads the per-vertex table of the current HPD weights
+    (_render_vertex_table; a trainable HPD is evaluated per call) and needs the lattice inside [0, 1]^2.
+    ValueError: should_batchnorm_data, a decoder other than [64, 64] with at most 4 outputs, L * F > 64, F not in {1, 2, 4} —
+    net(x) is the general path."""
+    rows, cols, r0, c0, denom, C = _render_setup(net, rows, cols, denom, origin)
+    rgb, image = bool(rgb) or out_rgb is not None, bool(image) or out_image is not None
+    if not (rgb or image):
+        raise ValueError("render(): ask for rgb, image or both")
+    tables = net.encoding.packed_tables()
+    dev = tables.device
+    if rgb and out_rgb is None:
+        out_rgb = torch.empty((rows * cols, C), dtype=torch.float32, device=dev)
+    if image and out_image is None:
+        out_image = torch.empty((rows, cols, C) if C != 1 else (rows, cols), dtype=torch.int32, device=dev)
+    for name, t, dt in (("out_rgb", out_rgb, torch.float32), ("out_image", out_image, torch.int32)):
+        if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() != rows * cols * C):
+            raise ValueError(f"{name} must be a contiguous device {dt} tensor of {rows} x {cols} x {C} elements")
+    ti = w = None
+    vstride = 0
+    if not net._hash_mode:
+        ti, w, vstride = _render_vertex_table(net)
+    ops.render_lattice(tables, net._n_ls_flat(dev), [p.detach() for p in net._decoder_params()], rows, cols, denom, (r0, c0),
+                       vert_idx=ti, vert_w=w, vstride=vstride, leaky=net._leaky, out_rgb=out_rgb if rgb else None,
+                       out_image=out_image if image else None)
+    if rgb and image:
+        return out_rgb, out_image
+    return out_rgb if rgb else out_image
+
+
+def render_psnr(net, og_image):
+    """Renders the model at og_image's own lattice — (h,w,3) or (h,w), whole values 0..255, what calc_psnr would be handed — and
+    scores it: (image int32 device tensor of og_image's shape, psnr, accuracy), the numbers formed as EpochImage.psnr() /
+    .accuracy() form them (integer sums on the device — gngf_image_metrics — floats on the host).  After fit():
+    `res.best.restore(); image, psnr, acc = render_psnr(net, og_image)` is the best model's picture and score."""
+    og = np.asarray(og_image)
+    if og.ndim not in (2, 3) or og.size == 0 or (og.ndim == 3 and not 1 <= og.shape[2] <= 4):
+        raise ValueError(f"og_image must be (h,w) or (h,w,C) with C <= 4, got {og.shape}")
+    t8 = og.astype(np.uint8)
+    if not np.array_equal(t8, og):
+        raise ValueError("og_image must hold whole values in 0..255")
+    h, w = int(og.shape[0]), int(og.shape[1])
+    C = 1 if og.ndim == 2 else int(og.shape[2])
+    if net.mlp[-1][0].weight.shape[0] != C:
+        raise ValueError(f"og_image has {C} channel(s), the model {net.mlp[-1][0].weight.shape[0]}")
+    img = render(net, h, w, rgb=False, image=True)
+    dev = img.device
+    n = h * w * C
+    sums = ops.image_metrics(img, torch.from_numpy(np.ascontiguousarray(t8).reshape(-1)).to(dev),
+                             torch.zeros((2,), dtype=torch.int64, device=dev), ops.image_metrics_workspace(n, dev))
+    eq, sse = sums.cpu().numpy()
+    return img.view(og.shape), float(psnr_from_sums(sse, n, 20 * np.log10(np.max(og_image)))), float((eq / n) * 100)

@@ -488,6 +488,22 @@ int gngf_image_metrics_blocks(int64_t n_elems);
 int gngf_image_metrics_workspace_words(int64_t n_elems);
 int gngf_image_metrics(const int32_t* img, const uint8_t* target, int64_t* sums, int64_t* workspace, int64_t n_elems, void* stream);
 
+/* ---- render: the model on a pixel lattice, forward only, one launch (csrc/render.inc) --------------------------------
+ * Pixel (r, c), r < rows, c < cols, has the coordinate ((float)(r0 + r) / denom, (float)(c0 + c) / denom) — one correctly
+ * rounded fp32 division per axis; no coordinate tensor is read — and row r cols + c of the outputs:
+ *   rgb (rows cols, out_dim) fp32 = decoder(encoding(coordinate)), the forward pass of gngf_encode_fwd + gngf_decoder_fwd
+ *   without the (P, L F) encoding in memory; img (same shape) int32 = (int32)(rgb * 255.0f), gngf_image_scatter's
+ *   quantisation.  Either may be NULL, not both.  No workspace, no synchronisation.
+ * tables (L,T,F) of feat_dtype, 16-byte aligned; mode GNGF_MODE_HASH, or GNGF_MODE_VERTEX_TABLE with vert_idx / vert_w
+ * (NV,K), vstride and NV as gngf_encode_fwd takes them (vertices outside the table are clamped; NV K < 2^31).
+ * Decoder W0 (64, L F), W1 (64,64), W2 (out_dim,64) and biases, hidden activation ReLU or (leaky) LeakyReLU(0.01).
+ * Requires F in {1,2,4}, L <= GNGF_MAX_LEVELS, L F <= 64, out_dim <= 4, rows, cols >= 1, denom > 0 and
+ * -2^24 <= r0, c0, r0 + rows <= 2^24, c0 + cols <= 2^24 (the integers are exact in fp32); else hipErrorInvalidValue. */
+int gngf_render(const void* tables, int feat_dtype, const int32_t* vert_idx, const float* vert_w, const int32_t* n_ls,
+                const float* W0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
+                float* rgb, int32_t* img, int64_t rows, int64_t cols, int64_t r0, int64_t c0, float denom,
+                int L, int F, int64_t T, int K, int mode, int vstride, int64_t NV, int out_dim, int leaky, void* stream);
+
 /* ---- epoch loop (functions.py:639-814: early stopping, the zero-collision stop, keeping the best model) ---------------
  * gngf_epoch_tail: one launch per epoch, one workgroup; takes the epoch's decisions on the device, advances `state` and
  * writes row e (the epoch's index, kept in the state) of the two logs.  No host synchronisation.

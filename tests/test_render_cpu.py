@@ -1,0 +1,141 @@
+"""CPU: the host side of the render feature — train.lattice_coordinates (the coordinates the kernel computes per pixel),
+argument validation of train.render, the presence of the gngf_render entry point — and the expected values of
+tests/test_gpu_render.py as far as they can be judged without a GPU (the oracle alone decides how much of an image lies in the
+integer rounding zone; rows of the committed 256 x 257 oracle output are recomputed)."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("h,w", [(7, 5), (61, 67), (256, 257)])
+def test_lattice_is_the_training_normalisation_bit_for_bit(h, w):
+    import torch
+    from collision_handling_in_instantngp_amd import data, train
+    got = train.lattice_coordinates(h, w, max(w, h) - 1)
+    want = data.normalise_coordinates(torch.from_numpy(data.pixel_grid(h, w)).float(), w, h).numpy()
+    assert got.dtype == np.float32 and got.shape == (h * w, 2) and got.flags["C_CONTIGUOUS"]
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+@pytest.mark.parametrize("s", [2, 3])
+@pytest.mark.parametrize("h,w", [(7, 5), (61, 67)])
+def test_upscale_contains_the_original_pixels(h, w, s):
+    from collision_handling_in_instantngp_amd import train
+    rows, cols, denom = (h - 1) * s + 1, (w - 1) * s + 1, (max(w, h) - 1) * s
+    dense = train.lattice_coordinates(rows, cols, denom).reshape(rows, cols, 2)[::s, ::s].reshape(-1, 2)
+    native = train.lattice_coordinates(h, w, max(w, h) - 1)
+    assert dense.shape == native.shape
+    # (k s) / (d s) and k / d are the same real number rounded once each: equal, or one ulp apart at most
+    assert np.all(np.abs(dense - native) <= np.spacing(np.maximum(dense, native)))
+    assert dense.min() == 0.0 and dense.max() == 1.0
+
+
+def test_origin_and_crop_are_consistent():
+    from collision_handling_in_instantngp_amd import train
+    full = train.lattice_coordinates(61, 67, 66).reshape(61, 67, 2)
+    part = train.lattice_coordinates(20, 30, 66, origin=(13, 21)).reshape(20, 30, 2)
+    assert np.array_equal(part, full[13:33, 21:51])
+    one = train.lattice_coordinates(1, 1, 1)
+    assert np.array_equal(one, np.zeros((1, 2), np.float32))
+    assert np.array_equal(train.lattice_coordinates(1, 1, 66, origin=(60, 66)), full[60:, 66:].reshape(1, 2))
+    assert train.lattice_coordinates(2, 2, 4, origin=(-2, -4)).min() == -1.0
+
+
+def test_lattice_argument_validation():
+    from collision_handling_in_instantngp_amd import train
+    for bad in (0, -3, float("nan")):
+        with pytest.raises(ValueError):
+            train.lattice_coordinates(4, 4, bad)
+    with pytest.raises(ValueError):
+        train.lattice_coordinates(0, 4, 3)
+    with pytest.raises(ValueError):
+        train.lattice_coordinates(4, 4, 3, origin=((1 << 24) - 3, 0))          # row indices past 2^24 are not exact in fp32
+    train.lattice_coordinates(4, 4, 3, origin=((1 << 24) - 4, 0))
+
+
+def _net(hash_mode, L=4, F=2, widths=(64, 64), T=64):
+    from collision_handling_in_instantngp_amd import models
+    prev = models.should_use_hash_function
+    models.should_use_hash_function = hash_mode
+    try:
+        return models.GeneralNeuralGaugeFields(input_dim=2, hash_table_size=T, num_levels=L, n_min=8, n_max=32,
+                                               MLP_hidden_layers_widths=list(widths), HPD_hidden_layers_widths=[8],
+                                               HPD_out_features=T, feature_dim=F, topk_k=2)
+    finally:
+        models.should_use_hash_function = prev
+
+
+def test_render_refuses_what_the_kernel_does_not_hold():
+    """every refusal is a ValueError raised before any device work, and names net(x) as the general path"""
+    from collision_handling_in_instantngp_amd import models, train
+    net = _net(True)
+    for kw in (dict(denom=0), dict(denom=-1.0), dict(rows=0), dict(origin=(1 << 24, 0))):
+        with pytest.raises(ValueError):
+            train.render(net, **{"rows": 8, "cols": 8, **kw})
+    with pytest.raises(ValueError, match="ask for rgb"):
+        train.render(net, 8, 8, rgb=False)
+    for bad, what in ((_net(True, widths=(64, 32)), "hidden widths"), (_net(True, widths=(64,)), "hidden widths"),
+                      (_net(True, L=9, F=8), "hidden widths|at most 64"), (_net(True, L=4, F=3), "1, 2 or 4")):
+        with pytest.raises(ValueError, match=what) as e:
+            train.render(bad, 8, 8)
+        assert "net(x)" in str(e.value)
+    models.should_batchnorm_data = True
+    try:
+        with pytest.raises(ValueError, match="should_batchnorm_data") as e:
+            train.render(net, 8, 8)
+        assert "net(x)" in str(e.value)
+    finally:
+        models.should_batchnorm_data = False
+    # GNGF indexing: the per-vertex table covers [0, 1]^2 only
+    gn = _net(False)
+    for kw in (dict(denom=6), dict(origin=(-1, 0)), dict(origin=(0, 1))):
+        with pytest.raises(ValueError, match=r"\[0, 1\]") as e:
+            train.render(gn, **{"rows": 8, "cols": 8, **kw})
+        assert "net(x)" in str(e.value)
+
+
+def test_entry_point_is_declared_exported_and_bound():
+    from collision_handling_in_instantngp_amd import _lib, ops, train
+    header = open(os.path.join(ROOT, "include", "gngf.h")).read()
+    assert re.search(r"\bint\s+gngf_render\s*\(", header)
+    assert "#define GNGF_ABI_VERSION 14" in header and _lib.ABI_VERSION == 14
+    assert len(_lib.SIGNATURES["gngf_render"]) == 28
+    lib = _lib.load()
+    assert hasattr(lib, "gngf_render") and lib.gngf_abi_version() == 14
+    assert callable(ops.render_lattice) and callable(train.render) and callable(train.render_psnr)
+    # rejected arguments come back as hipErrorInvalidValue before anything is launched (no device needed): F = 3, rows = 0,
+    # denom = 0, both outputs NULL
+    null = None
+    base = [null, 0, null, null, null, null, null, null, null, null, null, null, null, 8, 8, 0, 0, 7.0, 4, 2, 64, 0, 0, 0, 0, 3, 0, null]
+    assert lib.gngf_render(*base) == 1
+
+
+def test_oracle_values_keep_the_rounding_zone_small():
+    """the integer-image rule of tests/test_gpu_render.py allows a difference from the oracle only where oracle * 255 is within
+    the tolerance's reach of a whole number; from the oracle values alone: that is under 5 % of the elements (about 0.6 %)"""
+    import test_gpu_render as tr
+    for c in (tr.cfg(tr.FIRST, "hash", 4096), tr.cfg(tr.NARROW, "hash", 256), tr.cfg(tr.FIRST, "hash", 4096, bw=True)):
+        want = tr.want_rgb(c, 61, 67, 66)
+        assert want.shape == (61 * 67, 1 if c["bw"] else 3)
+        assert tr.rounding_zone(want).mean() < 0.05
+        # a picture, not one colour: the integer rule allows +-1, so an image confined to three adjacent integers could hide a
+        # wrong render inside it — every channel takes more distinct integer values than that
+        q = np.floor(want.astype(np.float64) * 255.0)
+        assert all(np.unique(q[:, k]).size > 3 for k in range(q.shape[1]))
+    big = np.load(tr.GOLDEN_256)["rgb"]
+    assert big.shape == (256 * 257, 3) and big.dtype == np.float32 and tr.rounding_zone(big).mean() < 0.05
+
+
+def test_committed_oracle_output_is_the_oracle():
+    """rows of tests/golden/render_gngf_256x257.npz recomputed by the literal oracle (256 pixels across the lattice)"""
+    import test_gpu_render as tr
+    from collision_handling_in_instantngp_amd import train
+    c = tr.cfg(tr.FIRST, "gngf", 256)
+    big = np.load(tr.GOLDEN_256)["rgb"]
+    rows = np.arange(0, 256 * 257, 257)
+    again = tr.oracle_rgb(c, tr.render_params(c), train.lattice_coordinates(256, 257, 256)[rows])
+    np.testing.assert_allclose(big[rows], again, rtol=0, atol=1e-7)
