@@ -1838,6 +1838,168 @@ vertex_bwd_sorted_kernel(const TT* __restrict__ tables, const int32_t* __restric
   if (live && dvert_w) dvert_w[e] = dw_acc;
 }
 
+// Vertex stage backward over a STATIC item list (frozen vertex table, no d w): everything vertex_bwd_sorted_kernel resolves
+// per step — order -> (vert_idx, vert_w) -> levels -> grid position, and where the equal-slot runs lie — is fixed between
+// two table builds, so ops.vertex_flat_list resolves it once: one item per (level, vertex, k) = (gi: index into the vertex
+// grid, w, dest: l * T + slot), sorted by dest.  The kernel is one flat segmented reduction: no level loop, no per-level
+// barrier, one gather per item with all of a thread's gathers in flight together.
+//   thread     kFlatIPT consecutive items (wide loads of gi / w / dest); runs that lie wholly inside it: one atomic each
+//   workgroup  the threads' open head / tail partials meet in ONE segmented scan (wave shuffles, then LDS across waves);
+//              one atomic per run that ends in, or crosses, the workgroup — no address gets more than one add per workgroup
+// The value of an item is formed exactly as vertex_bwd_sorted_kernel forms it (poison flag included).
+// measured at the headline shape (2.87 M items, us per launch): 256 threads x 4 items 16.2 | 512 x 4: 16.3 | 128 x 4: 19.9 |
+// 256 x 8: 19.7 | 128 x 8: 19.1; gathering a vertex's two 64-bit words in one 16-byte load instead of two 8-byte ones: 16.2 vs 16.4
+// (no gain: not kept)
+constexpr int kFlatTB = 256;       // threads per workgroup
+constexpr int kFlatIPT = 4;        // items per thread (one 16-byte load per static array)
+static_assert(kFlatIPT % 4 == 0 && kFlatTB % 64 == 0, "whole 16-byte loads, whole waves");
+template <int F, bool FROM64>
+__global__ void __launch_bounds__(kFlatTB)
+vertex_bwd_flat_kernel(const int32_t* __restrict__ item_gi, const float* __restrict__ item_w, const int32_t* __restrict__ item_dest,
+                       int64_t N, const float* __restrict__ dG, const unsigned long long* __restrict__ dG64, int64_t vtot,
+                       float* __restrict__ dtables, int64_t rows) {
+  constexpr int NW = kFlatTB / 64;
+  __shared__ int s_firstd[kFlatTB], s_lastd[kFlatTB];
+  __shared__ float s_y[kFlatTB][F];
+  __shared__ float s_wtot[NW][F];
+  __shared__ int s_wflag[NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t i0 = ((int64_t)blockIdx.x * kFlatTB + tid) * kFlatIPT;
+  int gi[kFlatIPT], d[kFlatIPT];
+  float w[kFlatIPT];
+  if (i0 + kFlatIPT <= N) {
+#pragma unroll
+    for (int c = 0; c < kFlatIPT; c += 4) {
+      const int4 g4 = *reinterpret_cast<const int4*>(item_gi + i0 + c);
+      const float4 w4 = *reinterpret_cast<const float4*>(item_w + i0 + c);
+      const int4 d4 = *reinterpret_cast<const int4*>(item_dest + i0 + c);
+      gi[c] = g4.x; gi[c + 1] = g4.y; gi[c + 2] = g4.z; gi[c + 3] = g4.w;
+      w[c] = w4.x; w[c + 1] = w4.y; w[c + 2] = w4.z; w[c + 3] = w4.w;
+      d[c] = d4.x; d[c + 1] = d4.y; d[c + 2] = d4.z; d[c + 3] = d4.w;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < kFlatIPT; ++i) {                     // the ragged end; items past it: dest -1, which is never emitted
+      const bool on = i0 + i < N;
+      gi[i] = on ? item_gi[i0 + i] : 0;
+      w[i] = on ? item_w[i0 + i] : 0.f;
+      d[i] = on ? item_dest[i0 + i] : -1;
+    }
+  }
+  // every gather of the thread is issued before the first one is used.  (The list is checked on the host when it is built;
+  // the clamp keeps a list that was not from reading outside the grid.)
+  float v[kFlatIPT][F];
+  if constexpr (FROM64) {
+    unsigned long long q[kFlatIPT][F];
+#pragma unroll
+    for (int i = 0; i < kFlatIPT; ++i) {
+      const int64_t g = gi[i] < 0 ? 0 : (gi[i] < vtot ? gi[i] : vtot - 1);
+#pragma unroll
+      for (int f = 0; f < F; ++f) q[i][f] = dG64[g * F + f];
+    }
+    const double inv64 = ldexp(1.0, -(int)(long long)dG64[vtot * F]);
+    const bool poisoned = dG64[vtot * F + 1] != 0ull;
+#pragma unroll
+    for (int i = 0; i < kFlatIPT; ++i)
+#pragma unroll
+      for (int f = 0; f < F; ++f)
+        v[i][f] = (poisoned ? __int_as_float(0x7fc00000) : (float)((double)(long long)q[i][f] * inv64)) * w[i];   // as vertex_bwd_sorted_kernel
+  } else {
+    float q[kFlatIPT][F];
+#pragma unroll
+    for (int i = 0; i < kFlatIPT; ++i) {
+      const int64_t g = gi[i] < 0 ? 0 : (gi[i] < vtot ? gi[i] : vtot - 1);
+#pragma unroll
+      for (int f = 0; f < F; ++f) q[i][f] = dG[g * F + f];
+    }
+#pragma unroll
+    for (int i = 0; i < kFlatIPT; ++i)
+#pragma unroll
+      for (int f = 0; f < F; ++f) v[i][f] = q[i][f] * w[i];
+  }
+  auto emit = [&](int dest, const float* s) {
+    if ((uint64_t)(int64_t)dest < (uint64_t)rows) {          // (dest -1: items past the end of the list)
+      float* p = dtables + (int64_t)dest * F;
+#pragma unroll
+      for (int f = 0; f < F; ++f)
+        if (s[f] != 0.f) atomicAdd(p + f, s[f]);
+    }
+  };
+  // the thread's own runs: the first one (head) and the last one (tail, = the head when there is no boundary inside the
+  // thread) stay open; the ones in between are complete
+  float acc[F], head[F];
+  int nb = 0;
+#pragma unroll
+  for (int f = 0; f < F; ++f) { acc[f] = v[0][f]; head[f] = 0.f; }
+#pragma unroll
+  for (int i = 1; i < kFlatIPT; ++i) {
+    if (d[i] != d[i - 1]) {
+      if (nb == 0) {
+#pragma unroll
+        for (int f = 0; f < F; ++f) head[f] = acc[f];
+      } else {
+        emit(d[i - 1], acc);
+      }
+      ++nb;
+#pragma unroll
+      for (int f = 0; f < F; ++f) acc[f] = v[i][f];
+    } else {
+#pragma unroll
+      for (int f = 0; f < F; ++f) acc[f] += v[i][f];
+    }
+  }
+  s_firstd[tid] = d[0];
+  s_lastd[tid] = d[kFlatIPT - 1];
+  __syncthreads();
+  const int prev_d = tid > 0 ? s_lastd[tid - 1] : -2;                   // (-2: equal to no dest, not even a dead item's)
+  const int next_d = tid + 1 < kFlatTB ? s_firstd[tid + 1] : -2;
+  // inclusive segmented scan of the tail partials over the workgroup's threads; a thread STARTS a segment when its tail run
+  // begins inside it, or at its first item
+  const int starts = (nb > 0 || prev_d != d[0]) ? 1 : 0;
+  float y[F];
+  int flag = starts;
+#pragma unroll
+  for (int f = 0; f < F; ++f) y[f] = acc[f];
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int fu = __shfl_up(flag, o, 64);
+    float yu[F];
+#pragma unroll
+    for (int f = 0; f < F; ++f) yu[f] = __shfl_up(y[f], o, 64);
+    if (lane >= o) {
+      if (!flag) {
+#pragma unroll
+        for (int f = 0; f < F; ++f) y[f] += yu[f];
+      }
+      flag |= fu;
+    }
+  }
+  if (lane == 63) {                                                      // the wave's open tail, and whether a segment starts in it
+#pragma unroll
+    for (int f = 0; f < F; ++f) s_wtot[wave][f] = y[f];
+    s_wflag[wave] = flag;
+  }
+  __syncthreads();
+  if (!flag) {                                                           // no segment has started in this wave up to this lane: the
+    for (int q = wave - 1; q >= 0; --q) {                                // run comes in from the waves below
+#pragma unroll
+      for (int f = 0; f < F; ++f) y[f] += s_wtot[q][f];
+      if (s_wflag[q]) break;
+    }
+  }
+#pragma unroll
+  for (int f = 0; f < F; ++f) s_y[tid][f] = y[f];
+  __syncthreads();
+  if (nb > 0) {                                                          // my head run ends inside me
+    if (tid > 0 && prev_d == d[0]) {
+#pragma unroll
+      for (int f = 0; f < F; ++f) head[f] += s_y[tid - 1][f];
+    }
+    emit(d[0], head);
+  }
+  if (next_d != d[kFlatIPT - 1]) emit(d[kFlatIPT - 1], y);               // my tail run ends with me (or leaves the workgroup)
+}
+
 }  // namespace gngf
 
 using namespace gngf;
@@ -2323,5 +2485,25 @@ extern "C" int gngf_vertex_grid_bwd_sorted(const void* tables, int feat_dtype, c
                                                                                  as_stream(stream)>>>(
                               static_cast<const TT*>(tables), vert_idx, vert_w, order, n_ls, dG, dtables, dvert_w, Ls, T, K,
                               vstride, NE, nullptr, 0))));
+  GNGF_RETURN_LAUNCH();
+}
+
+// Vertex stage backward over the static item list of a frozen vertex table (see vertex_bwd_flat_kernel; ops.vertex_flat_list
+// builds and checks the list).  item_gi / item_w / item_dest: N entries each, 16-byte aligned, sorted by dest; 0 <= gi < vtot,
+// 0 <= dest < rows = Ls * T.  The gradient is read from dG64 (with its scale and poison words) when it is given, else from dG.
+extern "C" int gngf_vertex_grid_bwd_flat(const int32_t* item_gi, const float* item_w, const int32_t* item_dest, int64_t N,
+                                         const float* dG, const void* dG64, int64_t vtot, float* dtables, int64_t rows, int F,
+                                         void* stream) {
+  GNGF_CHECK_ARG(item_gi && item_w && item_dest && N > 0 && N < (1ll << 31) && (dG || dG64) && vtot > 0 && dtables);
+  GNGF_CHECK_ARG(rows > 0 && rows < (1ll << 31));
+  GNGF_CHECK_ARG(((reinterpret_cast<uintptr_t>(item_gi) | reinterpret_cast<uintptr_t>(item_w) | reinterpret_cast<uintptr_t>(item_dest)) & 15) == 0);
+  const dim3 grid((unsigned)ceil_div(N, (int64_t)kFlatTB * kFlatIPT)), block(kFlatTB);
+  if (dG64) {
+    DISPATCH_F(F, (vertex_bwd_flat_kernel<kF, true><<<grid, block, 0, as_stream(stream)>>>(
+                      item_gi, item_w, item_dest, N, nullptr, static_cast<const unsigned long long*>(dG64), vtot, dtables, rows)));
+    GNGF_RETURN_LAUNCH();
+  }
+  DISPATCH_F(F, (vertex_bwd_flat_kernel<kF, false><<<grid, block, 0, as_stream(stream)>>>(item_gi, item_w, item_dest, N, dG, nullptr,
+                                                                                         vtot, dtables, rows)));
   GNGF_RETURN_LAUNCH();
 }

@@ -333,7 +333,10 @@ class GeneralNeuralGaugeFields(nn.Module):
             NV = vstride * vstride
             tv, ti, _, _ = ops.HpdVertexFunction.apply(NV, vstride, self._topk_k, None, False, HPD_CHUNK_BYTES, None, *params)
             w = ops.BlendFunction.apply(tv, blend_code)
-            self._frozen_table = (key, tv, ti, w, vstride, NV, ops.slot_order(ti, self._n_ls_host, vstride))
+            # (the static item lists of the flat vertex backward ride on `order`: rebuilt whenever this tuple is)
+            order = ops.attach_flat_lists(ops.slot_order(ti, self._n_ls_host, vstride), ti, w, self._n_ls_host, vstride,
+                                          self._hash_table_size)
+            self._frozen_table = (key, tv, ti, w, vstride, NV, order)
             if self._row_map is not None:
                 self._mark_reachable_rows(ti, vstride, NV)     # OR: the map covers every table used since it exists
         return self._frozen_table[1:]

@@ -1293,6 +1293,93 @@ def slot_order(vert_idx, n_ls_host=None, vstride=None):
     return torch.sort(flat, stable=True)[1].to(_i32)
 
 
+# VERTEX_BWD_FLAT (default 1) — frozen vertex table, no d w: the vertex stage backward runs over a static item list built once per
+# table (vertex_flat_list; gngf_vertex_grid_bwd_flat).  0: the slot-ordered kernel, as for every other case (A/B from one build).
+VERTEX_BWD_FLAT = 1
+# No list above this many items (12 bytes each: 48 MiB at the cap): the slot-ordered kernel runs instead.  The headline shape has
+# 2 866 176 items = 33 MiB beside 64 MiB of level tables; shapes whose vertex grids outgrow the cap (n_max 4096: 25 M vertices)
+# would pay more for reading the list than the per-step resolution it saves.
+VERTEX_BWD_FLAT_MAX_ITEMS = 1 << 22
+
+
+@_dc.dataclass(frozen=True)
+class VertexFlatList:
+    """The static item list of gngf_vertex_grid_bwd_flat (include/gngf.h), for levels [0, Ls) of one frozen vertex table."""
+    gi: object             # (n,) int32: index into the vertex grid
+    w: object              # (n,) fp32:  vert_w[vid, k]
+    dest: object           # (n,) int32: l * T + vert_idx[vid, k], ascending
+    n: int
+    Ls: int
+    T: int
+    vtot: int
+
+
+def vertex_flat_list(vert_idx, vert_w, n_ls_host, vstride, T):
+    """One item per (level l, vertex (gx, gy) of its (n_l+2)^2 grid, k): gi = goff[l] + gy (n_l+2) + gx, w = vert_w[vid, k], dest =
+    l T + vert_idx[vid, k] with vid = gy vstride + gx; stably sorted by dest, so gi ascends inside a run of equal dest.  Everything
+    the slot-ordered vertex backward resolves per step, resolved once per table build (plain torch: not the hot path).  The kernel
+    gathers through these indices, so their ranges are checked HERE, on the host: ValueError for a table with a slot outside
+    [0, T) or a vertex grid that does not fit the table.  None above VERTEX_BWD_FLAT_MAX_ITEMS."""
+    NV, K = vert_idx.shape
+    n_ls_host = [int(n) for n in n_ls_host]
+    Ls, vstride, T = len(n_ls_host), int(vstride), int(T)
+    vtot = sum((n + 2) * (n + 2) for n in n_ls_host)
+    if Ls == 0 or vtot * K > VERTEX_BWD_FLAT_MAX_ITEMS:
+        return None
+    if Ls * T >= 2 ** 31:
+        raise ValueError(f"vertex_flat_list: {Ls} levels of {T} rows do not fit a 32-bit row number")
+    dev = vert_idx.device
+    vids, lvls = [], []
+    for l, n in enumerate(n_ls_host):
+        gw = n + 2
+        if gw > vstride or (gw - 1) * vstride + gw > NV:
+            raise ValueError(f"vertex_flat_list: level {l}'s {gw} x {gw} vertex grid does not fit a table of {NV} vertices, stride {vstride}")
+        a = torch.arange(gw, device=dev, dtype=_i64)
+        vids.append((a[:, None] * vstride + a[None, :]).reshape(-1))           # gy-major, as the vertex grid
+        lvls.append(torch.full((gw * gw,), l, device=dev, dtype=_i64))
+    vid, lvl = torch.cat(vids), torch.cat(lvls)
+    slot = vert_idx[vid].to(_i64)                                              # (vtot, K)
+    lo, hi = int(slot.min()), int(slot.max())
+    if lo < 0 or hi >= T:
+        raise ValueError(f"vertex_flat_list: slots span [{lo}, {hi}], outside the table's [0, {T})")
+    dest, perm = torch.sort((lvl[:, None] * T + slot).reshape(-1), stable=True)
+    gi = torch.arange(vtot, device=dev, dtype=_i64).repeat_interleave(K)[perm]
+    w = vert_w.detach()[vid].reshape(-1)[perm].to(_f32)
+    n = vtot * K
+    assert gi.numel() == w.numel() == dest.numel() == n
+    if int(gi.min()) < 0 or int(gi.max()) >= vtot or int(dest[0]) < 0 or int(dest[-1]) >= Ls * T:
+        raise ValueError("vertex_flat_list: an index left its range")
+    return VertexFlatList(gi.to(_i32).contiguous(), w.contiguous(), dest.to(_i32).contiguous(), n, Ls, T, vtot)
+
+
+class VertexFlatLists:
+    """The item lists of ONE frozen vertex table, by staged level count (the plan of a batch decides how many levels the tiled form
+    takes): built at the first forward pass that wants one — never inside a graph capture — and kept as long as the table."""
+
+    def __init__(self, vert_idx, vert_w, n_ls_host, vstride, T):
+        self.vert_idx, self.vert_w = vert_idx, vert_w
+        self.n_ls_host, self.vstride, self.T = [int(n) for n in n_ls_host], int(vstride), int(T)
+        self._lists = {}
+
+    def get(self, Ls, vert_idx, vert_w, T):
+        """the list for levels [0, Ls) — None when it is not for these very tensors, above the cap, or not built yet and a capture is on"""
+        if vert_idx is not self.vert_idx or vert_w is not self.vert_w or int(T) != self.T or Ls > len(self.n_ls_host):
+            return None
+        if Ls not in self._lists:
+            if vert_idx.is_cuda and torch.cuda.is_current_stream_capturing():
+                return None
+            self._lists[Ls] = vertex_flat_list(vert_idx, vert_w, self.n_ls_host[:Ls], self.vstride, self.T)
+        return self._lists[Ls]
+
+
+def attach_flat_lists(order, vert_idx, vert_w, n_ls_host, vstride, T):
+    """Ties the (lazily built) item lists of a frozen vertex table to its cached slot_order(...): they travel with `order` through
+    encode_apply / EncodeFunction, live exactly as long as it does and are rebuilt whenever it is.  Returns `order`."""
+    if order is not None:
+        order.flat_lists = VertexFlatLists(vert_idx, vert_w, n_ls_host, vstride, T)
+    return order
+
+
 _TILE_LEVEL_OFF = {}
 
 
@@ -1325,7 +1412,7 @@ def tile_level_offsets(plan, device):
 
 # The kernel chain of one training step at the headline shape, as a string that changes whenever the chain does: PMC traffic
 # figures (profiles/traffic.json) are stamped with it and bench.py reports them only for the chain they were measured on.
-STEP_CHAIN_SIGNATURE = "r5: [bin_count_ride+bin_scatter2 | riders of the previous step] > tiled_fwd_il<SRC tables>(+count riders) > decoder_train > tiled_bwd_il(+scatter tasks, reduce, mse)<hash: HDT, table rows added by the store pass> [> vertex_bwd_sorted<FROM64> (vertex-table source)]"
+STEP_CHAIN_SIGNATURE = "r6: [bin_count_ride+bin_scatter2 | riders of the previous step] > tiled_fwd_il<SRC tables>(+count riders) > decoder_train > tiled_bwd_il(+scatter tasks, reduce, mse)<hash: HDT, table rows added by the store pass> [> vertex_bwd_flat<FROM64> over the static item list of the frozen table (vertex-table source; vertex_bwd_sorted<FROM64> without a list)]"
 # TUNING.fused_vertex_fwd (default True)      — fp32 tables on the interleaved forward kernel: the vertex stage forward runs inside its staging loop
 # TUNING.bin_pipeline (default True)          — ... and an announced next batch (BinPipeline) is binned by riders of this step's pixel-stage launches
 # F = 2, <= 16 staged levels, bounded |genc| (every source but the single-rank hash one below): the interleaved backward adds into a
@@ -1381,10 +1468,10 @@ def run_deferred_vertex_stage(dp, exchanged=False):
     other gradients)."""
     if dp is None or dp.deferred is None:
         return False
-    plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, order, gout = dp.deferred
+    plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, order, gout, flat = dp.deferred
     if dp.exchange is not None and not exchanged:
         dp.exchange(dG)
-    _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, None, order)
+    _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, None, order, **({"flat": flat} if flat is not None else {}))
     if gout is not None and gout is not dtables:
         # fp16 table storage: the gradient autograd received is a rounded COPY of the fp32 accumulation buffer, made before
         # the vertex stage ran.  Only the staged levels are refreshed (the direct levels' slice of `gout` may already hold
@@ -1393,9 +1480,24 @@ def run_deferred_vertex_stage(dp, exchanged=False):
     return True
 
 
-def _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw, order=None, dG64=None):
-    """dG64: the fixed-point vertex grid of _pixel_bwd(..., dG=None, dG64=...) read directly (slot-ordered form only)."""
+def _flat_list_of(order, plan, vert_idx, vert_w, T):
+    """the static item list that travels with a cached `order` (attach_flat_lists), for this plan's staged levels; None: none"""
+    lists = getattr(order, "flat_lists", None) if order is not None else None
+    if lists is None or not VERTEX_BWD_FLAT or vert_idx is None or plan.Ls <= 0:
+        return None
+    return lists.get(plan.Ls, vert_idx, vert_w, T)
+
+
+def _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw, order=None, dG64=None, flat=None):
+    """dG64: the fixed-point vertex grid of _pixel_bwd(..., dG=None, dG64=...) read directly (slot-ordered and flat forms only).
+    flat: the VertexFlatList of this (frozen) table for levels [0, plan.Ls) — without d w the flat segmented reduction runs."""
     L, T, F = tables.shape
+    if flat is not None and dvw is None and VERTEX_BWD_FLAT and vert_idx is not None and order is not None:
+        if (flat.Ls, flat.T, flat.vtot) != (plan.Ls, T, plan.vtot):
+            raise ValueError(f"the item list is for {flat.Ls} levels of {flat.T} rows, {flat.vtot} vertices: not this plan's")
+        call("gngf_vertex_grid_bwd_flat", ptr(flat.gi, _i32, "item_gi"), ptr(flat.w, _f32, "item_w"), ptr(flat.dest, _i32, "item_dest"),
+             flat.n, ptr(dG), ptr(dG64, _i64, "dG64"), plan.vtot, ptr(dtables, _f32, "dtables"), plan.Ls * T, F, stream_ptr())
+        return
     if vert_idx is not None and order is not None:
         call("gngf_vertex_grid_bwd_sorted", *_tab(tables), ptr(vert_idx), ptr(vert_w), ptr(order, _i32, "order"), ptr(n_ls), ptr(dG),
              ptr(dG64, _i64, "dG64"), plan.vtot, ptr(dtables), ptr(dvw), plan.Ls, F, T, vert_idx.shape[1], vstride, vert_idx.shape[0],
@@ -1448,22 +1550,26 @@ class StepConfig:
     clear: str             # who clears it: "decoder" (between its MFMAs) | "riders" (of the binning launch) | "rows" (sparse, persist) | "none"
     direct_bwd: str        # "bucketed_write" | "bucketed_or_atomics" (decided per call on the density) | "none"
     exchange: bool         # a data-parallel exchange of the vertex-grid gradient is set up
+    vertex_bwd_flat: bool = False      # vertex-table source: the backward of the vertex stage runs over the frozen table's static item list
 
     def signature(self):
         return (f"{self.source} L{self.staged}+{self.direct} bin={self.binning} vfwd={self.vertex_fwd} px={self.pixel} sink={self.grad_sink} "
-                f"dE={self.table_grad}/{self.clear} direct={self.direct_bwd}" + (" xchg" if self.exchange else ""))
+                f"dE={self.table_grad}/{self.clear} direct={self.direct_bwd}" + (" xchg" if self.exchange else "")
+                + (" vbwd=flat" if self.vertex_bwd_flat else ""))
 
     def chain(self):
         """the signature without the level COUNTS (the same kernels run whether 4 or 16 levels are staged): the key the test
-        coverage table of tests/test_step_config_cpu.py is written in"""
+        coverage table of tests/test_step_config_cpu.py is written in (vertex_bwd_flat is not part of it either: the same chain
+        with another kernel for its last launch, selected by the caller's cached table and ops.VERTEX_BWD_FLAT)"""
         lv = ("tiled" if self.staged else "") + ("+" if self.staged and self.direct else "") + ("direct" if self.direct else "")
         return (f"{self.source} {lv} bin={self.binning} vfwd={self.vertex_fwd} px={self.pixel} sink={self.grad_sink} "
                 f"dE={self.table_grad}/{self.clear} direct={self.direct_bwd}" + (" xchg" if self.exchange else ""))
 
     @staticmethod
     def choose(plan, L, T, F, P, mode, fp32_tables, needs_grad, link_defer_zero, link_zero_hidden, exchange, persist_ok, persist_alloc_ok,
-               have_reserve_ws):
-        """link_defer_zero / link_zero_hidden: the StepLink of the pass says a fused decoder kernel will clear the buffer it is left
+               have_reserve_ws, flat_list=False):
+        """flat_list: the static item list of a frozen vertex table is at hand and no d w is wanted (see vertex_bwd_flat).
+        link_defer_zero / link_zero_hidden: the StepLink of the pass says a fused decoder kernel will clear the buffer it is left
         (zero_hidden: the one-launch training kernel, which clears for free).  persist_alloc_ok: the step-to-step buffer exists or may
         be allocated now (not inside a capture).  have_reserve_ws: the persistent counters of the two-launch binning exist."""
         t = TUNING
@@ -1482,10 +1588,11 @@ class StepConfig:
             return StepConfig(src, plan.Ls, nd, "pipeline" if fused else "prepare", vf0,
                               "interleaved" if il_f else "generic", "none", "none", "none", "none", bool(exchange))
         use64 = F == 2 and plan.Ls <= 16 and il_b
+        vflat = bool(flat_list and mode != MODE_HASH)
         sink = "table_rows" if (mode == MODE_HASH and not exchange) else ("dG64" if use64 else "fp32_grid")
         if fused:
             return StepConfig(src, plan.Ls, nd, "pipeline", "fused", "interleaved", sink, "block", "decoder" if link_defer_zero else "riders",
-                              "bucketed_or_atomics" if nd > 0 else "none", bool(exchange))
+                              "bucketed_or_atomics" if nd > 0 else "none", bool(exchange), vflat)
         fresh = nd > 0 and mode == MODE_HASH and bucketed_plan(P, F, T, nd, True) is not None
         hidden = link_defer_zero and link_zero_hidden and L * T * F * 4 <= t.persistent_min_bytes
         persist = bool(t.persistent_table_grad and not hidden and mode == MODE_HASH and persist_ok and not exchange and (fresh or nd == 0)
@@ -1495,7 +1602,7 @@ class StepConfig:
         vf = "fused" if (t.fused_vertex_fwd and mode == MODE_HASH and not il_f) else "riders"
         return StepConfig(src, plan.Ls, nd, "prepare", vf, "interleaved" if il_b else "generic", sink,
                           "persist" if persist else "alloc", "rows" if persist else ("decoder" if link_defer_zero else "riders"),
-                          "bucketed_write" if fresh else ("bucketed_or_atomics" if nd > 0 else "none"), bool(exchange))
+                          "bucketed_write" if fresh else ("bucketed_or_atomics" if nd > 0 else "none"), bool(exchange), vflat)
 
 
 @_dc.dataclass
@@ -1525,6 +1632,9 @@ class EncodeFunction(torch.autograd.Function):
         NV = 0 if vert_idx is None else vert_idx.shape[0]
         enc = torch.empty((P, L * F), dtype=_f32, device=tables.device)
         ws = None
+        # a cached order of a frozen table brings the table's static item lists along (built here at first use, outside any capture)
+        ctx.flat = (_flat_list_of(order, plan, vert_idx, vert_w, T)
+                    if (P > 0 and ctx.needs_input_grad[3] and not ctx.needs_input_grad[5]) else None)
         if vert_idx is not None and order is None and plan.Ls > 0 and P > 0 and ctx.needs_input_grad[3]:
             order = slot_order(vert_idx, plan.n_ls_host[:plan.Ls], vstride)
         buf = None
@@ -1538,7 +1648,7 @@ class EncodeFunction(torch.autograd.Function):
             bool(link is not None and link.defer_zero), bool(link is not None and link.zero_hidden),
             bool(dp is not None and dp.exchange is not None), bool(dp is not None and dp.persist_ok and getattr(dp, "level_params", None)),
             bool(dp is not None and (getattr(dp, "persist_grad", None) is not None or not torch.cuda.is_current_stream_capturing())),
-            bool(pws is not None and pws.numel() >= 2 * plan.ntiles + 3))
+            bool(pws is not None and pws.numel() >= 2 * plan.ntiles + 3), flat_list=ctx.flat is not None)
         if dp is not None:
             dp.step_config = sc
         _trace("step_config", signature=sc.signature())
@@ -1712,7 +1822,7 @@ class EncodeFunction(torch.autograd.Function):
                     _direct_bwd(xy, tables, vert_idx, vert_w, n_ls, genc, dtables, dvw, P, L, F, T, K, mode, vstride, NV, plan.Ls, L,
                                 fresh=fresh_direct, order=(ws.sorted if ws is not None else None))
                 gout = _grad_out(dtables, tables, sink)
-                dp.deferred = (plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, order, gout)
+                dp.deferred = (plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, order, gout, ctx.flat)
                 dp.tables_reduced = plan.Ls
                 return (None, None, None, gout, None, dvw, *NONE)
             if exchange is not None:
@@ -1726,7 +1836,9 @@ class EncodeFunction(torch.autograd.Function):
                 _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw_t, order)
             else:
                 dvw_t = None
-                _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw, order, dG64 if direct64 else None)
+                # (the frozen table's static item list, when the forward pass found one: the flat segmented reduction)
+                _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw, order, dG64 if direct64 else None,
+                            **({"flat": ctx.flat} if ctx.flat is not None else {}))
         else:
             dvw_t = None
         if plan.Ls < L:

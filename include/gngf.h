@@ -241,6 +241,16 @@ int gngf_encode_tiled_bwd(const float* sorted, const int32_t* items, const int32
 int gngf_vertex_grid_bwd_sorted(const void* tables, int feat_dtype, const int32_t* vert_idx, const float* vert_w, const int32_t* order,
                                 const int32_t* n_ls, const float* dG, const void* dG64, int64_t vtot, float* dtables, float* dvert_w,
                                 int Ls, int F, int64_t T, int K, int vstride, int64_t NV, void* stream);
+/* the same stage over a STATIC item list, for a frozen vertex table without d w (additive: GNGF_ABI_VERSION stays 14).  One item
+ * per (level l < Ls, vertex (gx, gy) of that level's (N_l+2)^2 grid, k < K), N of them, stably sorted by dest:
+ *   item_gi = goff[l] + gy * (N_l+2) + gx  (index into the vertex grid, 0 <= gi < vtot),  item_w = vert_w[vid, k],
+ *   item_dest = l * T + vert_idx[vid, k]   (0 <= dest < rows = Ls * T),                   vid = gy * vstride + gx.
+ * The three arrays are 16-byte aligned and stay valid and unchanged while launches that read them are in flight; the caller has
+ * checked the ranges (the kernel gathers through item_gi).  One flat segmented reduction: no level loop, one atomic per run of
+ * equal dest that ends in or crosses a workgroup.  The gradient is read from dG64 when given (as above), else from dG (fp32);
+ * every value is formed as in gngf_vertex_grid_bwd_sorted, poison flag included.  dtables (rows, F) is accumulated into. */
+int gngf_vertex_grid_bwd_flat(const int32_t* item_gi, const float* item_w, const int32_t* item_dest, int64_t N, const float* dG,
+                              const void* dG64, int64_t vtot, float* dtables, int64_t rows, int F, void* stream);
 
 /* Large aligned GEMMs (full 128 x 128 tiles, contraction a multiple of 32) of the dense-layer entry points run on the
  * split-bf16 kernels while this is non-zero: every fp32 operand is split exactly into three bf16 terms and six of the nine cross

@@ -12,6 +12,7 @@ groups = {     # round 3 kernel names (the round-2 names stay listed: general sh
     "encode_bwd:tiled": ["gngf::tiled_bwd_kernel<2", "gngf::gather_partials_kernel<2", "gngf::tiled_bwd_il_kernel", "gngf::dg64_to_float_kernel"],
     "decoder_train": ["gngf::decoder_bwd_kernel<32, false, true, false, true, true>"],     # forward + backward in one launch
     "vertex_bwd": ["gngf::vertex_bwd_sorted_kernel<2", "gngf::vertex_bwd_kernel<2"],
+    "gngf_vertex_grid_bwd_flat": ["gngf::vertex_bwd_flat_kernel<2"],      # (bench.py lists this entry point under its own name)
     "encode_fwd:direct": ["gngf::encode_fwd_kernel"],
     "encode_bwd:direct": ["gngf::encode_bwd_kernel"],
     "encode_bwd:direct(bucketed)": ["gngf::bucket_count_kernel", "gngf::bucket_prefix_kernel", "gngf::bucket_scatter_kernel",
