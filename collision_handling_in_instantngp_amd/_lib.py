@@ -54,12 +54,11 @@ SIGNATURES = {
     "gngf_decoder_hidden_floats": [_L],
     "gngf_decoder_bwd_slabs": [_L],
     "gngf_decoder_slab_floats": [_I, _I],
-    "gngf_set_gemm_split_bf16": [_I],
     "gngf_set_decoder_bwd_hybrid": [_I],
-    "gngf_linear_fwd": [_P, _P, _P, _P, _L, _I, _I, _I, _P],
+    "gngf_linear_fwd": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
     "gngf_linear_bwd_input": [_P, _P, _P, _P, _L, _I, _I, _I, _P],
-    "gngf_linear_bwd_weight": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P],
-    "gngf_gemm_acc": [_P, _P, _P, _L, _L, _L, _I, _I, _P],
+    "gngf_linear_bwd_weight": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
+    "gngf_gemm_acc": [_P, _P, _P, _L, _L, _L, _I, _I, _I, _P],
     "gngf_softmax_topk": [_P, _P, _P, _P, _L, _L, _I, _P],
     "gngf_softmax_bwd_lowrank": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _L, _I, _P],
     "gngf_hpd_bwd_dot": [_P, _P, _P, _P, _P, _P, _I, _P, _L, _L, _I, _P],
@@ -105,7 +104,7 @@ SIGNATURES = {
     "gngf_snapshot_if": [_P, _I, _L, _P, _P],
 }
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class BinJob(ctypes.Structure):

@@ -363,8 +363,8 @@ gemm128_fast_kernel(const float* __restrict__ A, const float* __restrict__ B, fl
 // fma chain over the same K accumulates — while the bf16 matrix pipe runs 16x the fp32 one per instruction: six bf16 MFMAs
 // cost 3/8 of the fp32 MFMA they replace, and the VALU work of the splitting issues in the bf16 MFMA's free issue slots
 // (an fp32 MFMA shares the fp32 ALUs with VALU instructions; a bf16 MFMA does not).  Used for the T-wide last layer of
-// the HashProbDistribution (logits, dW, dh: 3 x 2.4e13 FLOP per training step at T = 2^19), switchable
-// (gngf_set_gemm_split_bf16) — the exact-fp32 kernel above stays the default for everything else.
+// the HashProbDistribution (logits, dW, dh: 3 x 2.4e13 FLOP per training step at T = 2^19), chosen per call
+// (the entry points' gemm argument) — the exact-fp32 kernel above stays the default for everything else.
 using bf16x8_t = __attribute__((ext_vector_type(8))) __bf16;
 __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
   unsigned d;
@@ -492,8 +492,7 @@ template <bool TA, bool TB>
 __global__ void __launch_bounds__(256, GNGF_SPLIT_WGS)
 gemm128_split_kernel(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ C,
                      int64_t lda, int64_t ldb, int64_t ldc, const float* __restrict__ bias, int act, int64_t K,
-                     int64_t kchunk, int atomic_out, int tiles_m, int tiles_n, float2* __restrict__ rowparts = nullptr,
-                     int nparts = 0) {
+                     int64_t kchunk, int atomic_out, int tiles_m, int tiles_n) {
   constexpr int BKF = 32;
   constexpr int NV4 = BKF / 8;
   __shared__ float As[BKF * LDS2];
@@ -574,7 +573,7 @@ gemm128_split_kernel(const float* __restrict__ A, const float* __restrict__ B, f
     });
     __syncthreads();
   }
-  split_epilogue(acc, C, ldc, bias, act, atomic_out, m0, n0, wm, wn, i, h, rowparts, nparts);
+  split_epilogue(acc, C, ldc, bias, act, atomic_out, m0, n0, wm, wn, i, h, nullptr, 0);
 }
 
 // ---------------------------------------------------------------------------------- split once, bf16 planes in LDS
@@ -1165,8 +1164,6 @@ hpd_topk_side_kernel(const float* __restrict__ pk, const float* __restrict__ dq,
   if (c == 0 && db) atomicAdd(db + slot, a);
 }
 
-static int g_split_bf16 = 0;       // see gngf_set_gemm_split_bf16
-
 // column sums of dZ = dY * act'(Y):  db[n] = sum_m dZ[m][n].  grid.x = ceil(N/64), grid.y = row slices; atomics.
 __global__ void __launch_bounds__(256)
 colsum_kernel(const float* __restrict__ dY, const float* __restrict__ Ymask, int mask_act, float* __restrict__ db,
@@ -1188,25 +1185,16 @@ colsum_kernel(const float* __restrict__ dY, const float* __restrict__ Ymask, int
   if (rsub == 0 && col < N) atomicAdd(db + col, (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]));
 }
 
+// Which kernel a product runs on is an argument of the call (gemm: a GNGF_GEMM_* code of include/gngf.h).
+static bool gemm_code_ok(int gemm) {
+  return gemm == GNGF_GEMM_FP32 || gemm == GNGF_GEMM_PLANES || gemm == GNGF_GEMM_PLANES_ACC2 || gemm == GNGF_GEMM_WAVE_SPLIT;
+}
+
 template <bool TA, bool TB>
 static int launch_gemm(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
-                       int64_t ldc, const float* bias, int act, const float* amask, int mask_act, int splitk,
+                       int64_t ldc, const float* bias, int act, const float* amask, int mask_act, int splitk, int gemm,
                        hipStream_t s, bool force_atomic = false, float2* rowparts = nullptr) {
   if (M == 0 || N == 0) return 0;
-  if (rowparts) {      // row statistics in the epilogue: the split-bf16 128 x 128 kernel only, whole tiles, one K slice, plain stores
-    const bool aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && lda % 4 == 0 && ldb % 4 == 0;
-    const bool windows32 = lda < (1 << 22) && ldb < (1 << 22) && ldc < (1 << 22);
-    if (!(M % BM2 == 0 && N % BN2 == 0 && K % 32 == 0 && !amask && aligned && windows32 && splitk <= 1 && !force_atomic && act == 0))
-      return (int)hipErrorInvalidValue;
-    const unsigned tm_ = (unsigned)(M / BM2), tn_ = (unsigned)(N / BN2);
-    if (g_split_bf16 == 17)
-      gemm128_split_kernel<TA, TB><<<dim3(tm_ * tn_, 1), dim3(256), 0, s>>>(A, B, C, lda, ldb, ldc, bias, act, K, K, 0, (int)tm_, (int)tn_,
-                                                                         rowparts, (int)(N / 64));
-    else
-      gemm128_planes_kernel<TA, TB, 3><<<dim3(tm_ * tn_, 1), dim3(256), 0, s>>>(A, B, C, lda, ldb, ldc, bias, act, K, K, 0, (int)tm_, (int)tn_,
-                                                                             rowparts, (int)(N / 64));
-    return (int)hipGetLastError();
-  }
   int64_t kchunk = K;
   if (splitk > 1) {
     kchunk = ceil_div(ceil_div(K, splitk), BK) * BK;
@@ -1214,41 +1202,31 @@ static int launch_gemm(const float* A, const float* B, float* C, int64_t M, int6
   } else {
     splitk = 1;
   }
-  if (M >= BM2 && N >= BN2) {          // large problems: 128x128 tiles, 2x2 accumulators per wave
-    dim3 grid2((unsigned)ceil_div(N, BN2), (unsigned)ceil_div(M, BM2), (unsigned)splitk);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && lda % 4 == 0 && ldb % 4 == 0;
-    const bool windows32 = lda < (1 << 22) && ldb < (1 << 22) && ldc < (1 << 22);   // 128 rows * ld * 4 B < 2^31
-    if (M % BM2 == 0 && N % BN2 == 0 && !amask && aligned && windows32) {
-      const dim3 gridf(grid2.x * grid2.y, (unsigned)splitk);
-      if (g_split_bf16 && K % 32 == 0 && kchunk % 32 == 0) {
-        const int ato = (splitk > 1 || force_atomic) ? 1 : 0;
-        // two planes only where the result is ACCUMULATED over a long contraction (the backward pass's dW and dh: force_atomic)
-        if (g_split_bf16 == 2 && force_atomic)
-          gemm128_planes_kernel<TA, TB, 2><<<gridf, dim3(256), 0, s>>>(A, B, C, lda, ldb, ldc, bias, act, K, kchunk, ato, (int)grid2.y, (int)grid2.x);
-        else if (g_split_bf16 == 17)
-          gemm128_split_kernel<TA, TB><<<gridf, dim3(256), 0, s>>>(A, B, C, lda, ldb, ldc, bias, act, K, kchunk, ato, (int)grid2.y, (int)grid2.x);
-        else
-          gemm128_planes_kernel<TA, TB, 3><<<gridf, dim3(256), 0, s>>>(A, B, C, lda, ldb, ldc, bias, act, K, kchunk, ato, (int)grid2.y, (int)grid2.x);
-        return (int)hipGetLastError();
-      }
-      if (K % kFastBK == 0 && kchunk % kFastBK == 0) {
-        gemm128_fast_kernel<TA, TB, kFastBK><<<gridf, dim3(256), 0, s>>>(A, B, C, lda, ldb, ldc, bias, act, K, kchunk,
-                                                                        (splitk > 1 || force_atomic) ? 1 : 0, (int)grid2.y, (int)grid2.x);
-        return (int)hipGetLastError();
-      }
-      if (K % BK == 0 && kchunk % BK == 0) {
-        gemm128_fast_kernel<TA, TB, BK><<<gridf, dim3(256), 0, s>>>(A, B, C, lda, ldb, ldc, bias, act, K, kchunk,
-                                                                   (splitk > 1 || force_atomic) ? 1 : 0, (int)grid2.y, (int)grid2.x);
-        return (int)hipGetLastError();
-      }
-    }
-    gemm128_kernel<TA, TB><<<grid2, dim3(256), 0, s>>>(A, B, C, M, N, K, lda, ldb, ldc, bias, act, amask, mask_act, kchunk,
-                                                      (splitk > 1 || force_atomic) ? 1 : 0);
+  const int atomic_out = (splitk > 1 || force_atomic) ? 1 : 0;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && lda % 4 == 0 && ldb % 4 == 0;
+  const bool windows32 = lda < (1 << 22) && ldb < (1 << 22) && ldc < (1 << 22);   // 128 rows * ld * 4 B < 2^31
+  const bool whole_tiles = M % BM2 == 0 && N % BN2 == 0 && !amask && aligned && windows32;
+  const bool split = gemm != GNGF_GEMM_FP32 && whole_tiles && K % 32 == 0 && kchunk % 32 == 0;
+  // row statistics in the epilogue: the three-plane kernel only, one K slice, plain stores, no activation
+  if (rowparts && !(split && gemm == GNGF_GEMM_PLANES && !atomic_out && act == 0)) return (int)hipErrorInvalidValue;
+  if (M < BM2 || N < BN2) {
+    const dim3 grid((unsigned)ceil_div(N, BN), (unsigned)ceil_div(M, BM), (unsigned)splitk);
+    gemm_kernel<TA, TB><<<grid, dim3(256), 0, s>>>(A, B, C, M, N, K, lda, ldb, ldc, bias, act, amask, mask_act, kchunk, atomic_out);
     return (int)hipGetLastError();
   }
-  dim3 grid((unsigned)ceil_div(N, BN), (unsigned)ceil_div(M, BM), (unsigned)splitk);
-  gemm_kernel<TA, TB><<<grid, dim3(256), 0, s>>>(A, B, C, M, N, K, lda, ldb, ldc, bias, act, amask, mask_act, kchunk,
-                                                (splitk > 1 || force_atomic) ? 1 : 0);
+  // large problems: 128x128 tiles, 2x2 accumulators per wave; whole tiles take one of the kernels that walk a flat tile index
+  const dim3 grid2((unsigned)ceil_div(N, BN2), (unsigned)ceil_div(M, BM2), (unsigned)splitk);
+  auto tiled = [&](auto kernel, auto... extra) {
+    kernel<<<dim3(grid2.x * grid2.y, (unsigned)splitk), dim3(256), 0, s>>>(A, B, C, lda, ldb, ldc, bias, act, K, kchunk, atomic_out,
+                                                                         (int)grid2.y, (int)grid2.x, extra...);
+  };
+  // two planes only where the result is ACCUMULATED over a long contraction (the backward pass's dW and dh: force_atomic)
+  if (split && gemm == GNGF_GEMM_PLANES_ACC2 && force_atomic) tiled(gemm128_planes_kernel<TA, TB, 2>, (float2*)nullptr, 0);
+  else if (split && gemm == GNGF_GEMM_WAVE_SPLIT) tiled(gemm128_split_kernel<TA, TB>);
+  else if (split) tiled(gemm128_planes_kernel<TA, TB, 3>, rowparts, (int)(N / 64));
+  else if (whole_tiles && K % kFastBK == 0 && kchunk % kFastBK == 0) tiled(gemm128_fast_kernel<TA, TB, kFastBK>);
+  else if (whole_tiles && K % BK == 0 && kchunk % BK == 0) tiled(gemm128_fast_kernel<TA, TB, BK>);
+  else gemm128_kernel<TA, TB><<<grid2, dim3(256), 0, s>>>(A, B, C, M, N, K, lda, ldb, ldc, bias, act, amask, mask_act, kchunk, atomic_out);
   return (int)hipGetLastError();
 }
 
@@ -1256,33 +1234,34 @@ static int launch_gemm(const float* A, const float* B, float* C, int64_t M, int6
 
 using namespace gngf;
 
-// Large aligned GEMMs (full 128 x 128 tiles, K % 32 == 0) of the entry points below run on the split-bf16 kernel while this
-// is on (process-wide switch; returns the previous setting).  Off by default.
-extern "C" int gngf_set_gemm_split_bf16(int on) {
-  const int prev = g_split_bf16;
-  g_split_bf16 = (on == 2 || on == 17) ? on : (on ? 1 : 0);
-  return prev;
-}
+#define DISPATCH_PLANES(planes, ...)                          \
+  if ((planes) == 2) { constexpr int NP = 2; __VA_ARGS__; }   \
+  else if ((planes) == 3) { constexpr int NP = 3; __VA_ARGS__; } \
+  else return (int)hipErrorInvalidValue;
+
+// gemm (gngf_linear_fwd, gngf_linear_bwd_weight, gngf_gemm_acc): a split code runs large aligned products (whole 128 x 128 tiles,
+// contraction and K slice multiples of 32, no masked operand, 32-bit windows) on the split-bf16 kernels; every other shape takes the
+// exact-fp32 kernels whatever the code.
 
 // Y[M,N] = act(X[M,K] * W[N,K]^T + b)          nn.Linear + activation (models.py:84-85, 386-389)
 extern "C" int gngf_linear_fwd(const float* X, const float* W, const float* b, float* Y, int64_t M, int N, int K, int act,
-                               void* stream) {
-  GNGF_CHECK_ARG(M >= 0 && N > 0 && K > 0 && act >= 0 && act <= 3);
+                               int gemm, void* stream) {
+  GNGF_CHECK_ARG(M >= 0 && N > 0 && K > 0 && act >= 0 && act <= 3 && gemm_code_ok(gemm));
   if (M == 0) return 0;
   GNGF_CHECK_ARG(X && W && Y);
-  return launch_gemm<false, true>(X, W, Y, M, N, K, K, K, N, b, act, nullptr, 0, 1, as_stream(stream));
+  return launch_gemm<false, true>(X, W, Y, M, N, K, K, K, N, b, act, nullptr, 0, 1, gemm, as_stream(stream));
 }
 
 // The same product (no activation) with ROW STATISTICS of Y in the epilogue: rowparts (M, N / 64) pairs (max, sum exp(y - max)) over
 // each row's 64-column blocks, for gngf_rowstats_topk.  Only for whole 128 x 128 tiles (M % 128 == 0, N % 128 == 0, K % 32 == 0,
 // 16-byte aligned operands): anything else is rejected (the caller then takes gngf_linear_fwd + gngf_logits_topk_pbar).  Always on
-// the split-bf16 kernel (exact three-way split, fp32 accumulation).
+// the three-plane split-bf16 kernel (exact three-way split, fp32 accumulation).
 extern "C" int gngf_linear_fwd_rowstats(const float* X, const float* W, const float* b, float* Y, float* rowparts, int64_t M, int N,
                                         int K, void* stream) {
   GNGF_CHECK_ARG(M >= 0 && N > 0 && K > 0);
   if (M == 0) return 0;
   GNGF_CHECK_ARG(X && W && Y && rowparts);
-  return launch_gemm<false, true>(X, W, Y, M, N, K, K, K, N, b, 0, nullptr, 0, 1, as_stream(stream), false,
+  return launch_gemm<false, true>(X, W, Y, M, N, K, K, K, N, b, 0, nullptr, 0, 1, GNGF_GEMM_PLANES, as_stream(stream), false,
                                   reinterpret_cast<float2*>(rowparts));
 }
 
@@ -1292,14 +1271,14 @@ extern "C" int gngf_linear_bwd_input(const float* dY, const float* Y, const floa
   GNGF_CHECK_ARG(M >= 0 && N > 0 && K > 0 && act >= 0 && act <= 3);
   if (M == 0) return 0;
   GNGF_CHECK_ARG(dY && W && dX && (act == 0 || Y));
-  return launch_gemm<false, false>(dY, W, dX, M, K, N, N, K, K, nullptr, 0, act ? Y : nullptr, act, 1, as_stream(stream));
+  return launch_gemm<false, false>(dY, W, dX, M, K, N, N, K, K, nullptr, 0, act ? Y : nullptr, act, 1, GNGF_GEMM_FP32, as_stream(stream));
 }
 
 // dW[N,K] += (dY .* act'(Y))^T * X ;  db[N] += colsum(dY .* act'(Y)).   dW and db must be zero-filled by the caller
 // when a fresh gradient is wanted (split over the M contraction, accumulated with float atomics).
 extern "C" int gngf_linear_bwd_weight(const float* dY, const float* Y, const float* X, float* dW, float* db, int64_t M, int N,
-                                      int K, int act, void* stream) {
-  GNGF_CHECK_ARG(M >= 0 && N > 0 && K > 0 && act >= 0 && act <= 3);
+                                      int K, int act, int gemm, void* stream) {
+  GNGF_CHECK_ARG(M >= 0 && N > 0 && K > 0 && act >= 0 && act <= 3 && gemm_code_ok(gemm));
   if (M == 0) return 0;
   GNGF_CHECK_ARG(dY && X && dW && (act == 0 || Y));
   const int tsz = (N >= BM2 && K >= BN2) ? BM2 : BM;
@@ -1307,7 +1286,7 @@ extern "C" int gngf_linear_bwd_weight(const float* dY, const float* Y, const flo
   int splitk = (int)((1024 + tiles - 1) / tiles);
   const int64_t max_split = ceil_div(M, 256);
   if (splitk > max_split) splitk = (int)max_split;
-  int rc = launch_gemm<true, false>(dY, X, dW, N, K, M, N, K, K, nullptr, 0, act ? Y : nullptr, act, splitk, as_stream(stream),
+  int rc = launch_gemm<true, false>(dY, X, dW, N, K, M, N, K, K, nullptr, 0, act ? Y : nullptr, act, splitk, gemm, as_stream(stream),
                                     /*force_atomic=*/true);
   if (rc) return rc;
   if (db) {
@@ -1325,8 +1304,8 @@ extern "C" int gngf_linear_bwd_weight(const float* dY, const float* Y, const flo
 // blocks (float atomics; C zero-filled by the caller for a fresh result).
 //   ta = 0: A is (M,Kc) row-major, ta = 1: A is (Kc,M) row-major;  tb = 0: B is (Kc,N), tb = 1: B is (N,Kc).
 extern "C" int gngf_gemm_acc(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kc, int ta, int tb,
-                             void* stream) {
-  GNGF_CHECK_ARG(M >= 0 && N >= 0 && Kc >= 0);
+                             int gemm, void* stream) {
+  GNGF_CHECK_ARG(M >= 0 && N >= 0 && Kc >= 0 && gemm_code_ok(gemm));
   if (M == 0 || N == 0 || Kc == 0) return 0;
   GNGF_CHECK_ARG(A && B && C);
   const int tsz = (M >= BM2 && N >= BN2) ? BM2 : BM;
@@ -1337,10 +1316,10 @@ extern "C" int gngf_gemm_acc(const float* A, const float* B, float* C, int64_t M
   if (splitk < 1) splitk = 1;
   const int64_t lda = ta ? M : Kc, ldb = tb ? Kc : N;
   hipStream_t s = as_stream(stream);
-  if (!ta && !tb) return launch_gemm<false, false>(A, B, C, M, N, Kc, lda, ldb, N, nullptr, 0, nullptr, 0, splitk, s, true);
-  if (!ta && tb) return launch_gemm<false, true>(A, B, C, M, N, Kc, lda, ldb, N, nullptr, 0, nullptr, 0, splitk, s, true);
-  if (ta && !tb) return launch_gemm<true, false>(A, B, C, M, N, Kc, lda, ldb, N, nullptr, 0, nullptr, 0, splitk, s, true);
-  return launch_gemm<true, true>(A, B, C, M, N, Kc, lda, ldb, N, nullptr, 0, nullptr, 0, splitk, s, true);
+  if (!ta && !tb) return launch_gemm<false, false>(A, B, C, M, N, Kc, lda, ldb, N, nullptr, 0, nullptr, 0, splitk, gemm, s, true);
+  if (!ta && tb) return launch_gemm<false, true>(A, B, C, M, N, Kc, lda, ldb, N, nullptr, 0, nullptr, 0, splitk, gemm, s, true);
+  if (ta && !tb) return launch_gemm<true, false>(A, B, C, M, N, Kc, lda, ldb, N, nullptr, 0, nullptr, 0, splitk, gemm, s, true);
+  return launch_gemm<true, true>(A, B, C, M, N, Kc, lda, ldb, N, nullptr, 0, nullptr, 0, splitk, gemm, s, true);
 }
 
 // Does gngf_hpd_bwd_fused take this shape?  (whole 128-row / 128-column tiles, last hidden width 128, L <= 16, 32-bit windows)
@@ -1360,14 +1339,14 @@ extern "C" int gngf_hpd_bwd_prepare(const float* h, const float* mw, int64_t row
   if (h && rows > 0) {
     GNGF_CHECK_ARG(hp && mwp && (L == 0 || mw));
     const dim3 g((unsigned)ceil_div(rows * 128 / 8, 256));
-    if (planes == 2) hpd_prepare_kernel<2><<<g, dim3(256), 0, s>>>(h, static_cast<unsigned short*>(hp), mw, L, L, 1, static_cast<unsigned short*>(mwp), rows);
-    else hpd_prepare_kernel<3><<<g, dim3(256), 0, s>>>(h, static_cast<unsigned short*>(hp), mw, L, L, 1, static_cast<unsigned short*>(mwp), rows);
+    DISPATCH_PLANES(planes, (hpd_prepare_kernel<NP><<<g, dim3(256), 0, s>>>(h, static_cast<unsigned short*>(hp), mw, L, L, 1,
+                                                                           static_cast<unsigned short*>(mwp), rows)));
   }
   if (W && T > 0) {
     GNGF_CHECK_ARG(Wp && Gtp && (L == 0 || G));
     const dim3 g((unsigned)ceil_div(T * 128 / 8, 256));
-    if (planes == 2) hpd_prepare_kernel<2><<<g, dim3(256), 0, s>>>(W, static_cast<unsigned short*>(Wp), G, L, 1, T, static_cast<unsigned short*>(Gtp), T);
-    else hpd_prepare_kernel<3><<<g, dim3(256), 0, s>>>(W, static_cast<unsigned short*>(Wp), G, L, 1, T, static_cast<unsigned short*>(Gtp), T);
+    DISPATCH_PLANES(planes, (hpd_prepare_kernel<NP><<<g, dim3(256), 0, s>>>(W, static_cast<unsigned short*>(Wp), G, L, 1, T,
+                                                                           static_cast<unsigned short*>(Gtp), T)));
   }
   GNGF_RETURN_LAUNCH();
 }
@@ -1396,13 +1375,10 @@ extern "C" int gngf_hpd_bwd_fused(const float* logits, const float* rowstat, con
   int64_t kchunk = ceil_div(ceil_div(T, slices), 64) * 64;
   slices = ceil_div(T, kchunk);
   const dim3 gh((unsigned)(rtiles * slices));
-  if (planes == 2) {
-    if (only == 0 || only == 1) hpd_dw_fused_kernel<2><<<gw, dim3(256), 0, s>>>(logits, rowstat, dot, mwp_, Gtp_, hp_, rows_total, dW, db, U, T);
-    if (only == 0 || only == 2) hpd_dh_fused_kernel<2><<<gh, dim3(256), 0, s>>>(logits, rowstat, dot, mwp_, Gtp_, Wp_, rows_total, dH, U, T, kchunk, (int)rtiles, (int)slices);
-  } else {
-    if (only == 0 || only == 1) hpd_dw_fused_kernel<3><<<gw, dim3(256), 0, s>>>(logits, rowstat, dot, mwp_, Gtp_, hp_, rows_total, dW, db, U, T);
-    if (only == 0 || only == 2) hpd_dh_fused_kernel<3><<<gh, dim3(256), 0, s>>>(logits, rowstat, dot, mwp_, Gtp_, Wp_, rows_total, dH, U, T, kchunk, (int)rtiles, (int)slices);
-  }
+  DISPATCH_PLANES(planes, {
+    if (only == 0 || only == 1) hpd_dw_fused_kernel<NP><<<gw, dim3(256), 0, s>>>(logits, rowstat, dot, mwp_, Gtp_, hp_, rows_total, dW, db, U, T);
+    if (only == 0 || only == 2) hpd_dh_fused_kernel<NP><<<gh, dim3(256), 0, s>>>(logits, rowstat, dot, mwp_, Gtp_, Wp_, rows_total, dH, U, T, kchunk, (int)rtiles, (int)slices);
+  });
   if (K > 0 && (only == 0 || only == 3))
     hpd_topk_side_kernel<<<dim3((unsigned)(U * K)), dim3(128), 0, s>>>(topk_p, dq, topk_idx, h, W, dW, db, dH, K);
   GNGF_RETURN_LAUNCH();

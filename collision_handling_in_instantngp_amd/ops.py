@@ -365,15 +365,19 @@ class EncodeDirectFunction(torch.autograd.Function):
 
 # ------------------------------------------------------------------------------------------------ dense layers
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
+# GNGF_GEMM_*: the kernel of ONE product (an argument of linear_fwd / linear_bwd_weight / gemm_acc): exact fp32 MFMA | three bf16
+# planes | three planes, two where the entry accumulates | the per-wave split kernel.  Shapes the split kernels do not take run fp32.
+GEMM_FP32, GEMM_PLANES, GEMM_PLANES_ACC2, GEMM_WAVE_SPLIT = 0, 1, 2, 17
 
 
-def linear_fwd(x, w, b, act, y=None):
+def linear_fwd(x, w, b, act, y=None, gemm=GEMM_FP32):
     """y (M,N) = act(x w^T + b), into `y` where one is given."""
     M, K = x.shape
     N = w.shape[0]
     if y is None:
         y = torch.empty((M, N), dtype=_f32, device=x.device)
-    call("gngf_linear_fwd", ptr(x, _f32, "x"), ptr(w, _f32, "weight"), ptr(b, _f32, "bias"), ptr(y), M, N, K, act, stream_ptr())
+    call("gngf_linear_fwd", ptr(x, _f32, "x"), ptr(w, _f32, "weight"), ptr(b, _f32, "bias"), ptr(y), M, N, K, act, gemm,
+         stream_ptr())
     return y
 
 
@@ -385,17 +389,17 @@ def linear_bwd_input(dy, y, w, act):
     return dx
 
 
-def linear_bwd_weight(dy, y, x, dw, db, act):
+def linear_bwd_weight(dy, y, x, dw, db, act, gemm=GEMM_FP32):
     """Accumulates into dw (N,K) and db (N,)."""
     M, N = dy.shape
     K = x.shape[1]
     call("gngf_linear_bwd_weight", ptr(dy, _f32), ptr(y if act else None, _f32), ptr(x, _f32), ptr(dw, _f32),
          ptr(db, _f32) if db is not None else ptr(None),
-         M, N, K, act, stream_ptr())
+         M, N, K, act, gemm, stream_ptr())
 
 
-def gemm_acc(a, b, c, M, N, Kc, ta, tb):
-    call("gngf_gemm_acc", ptr(a, _f32), ptr(b, _f32), ptr(c, _f32), M, N, Kc, int(ta), int(tb), stream_ptr())
+def gemm_acc(a, b, c, M, N, Kc, ta, tb, gemm=GEMM_FP32):
+    call("gngf_gemm_acc", ptr(a, _f32), ptr(b, _f32), ptr(c, _f32), M, N, Kc, int(ta), int(tb), gemm, stream_ptr())
 
 
 class MlpFunction(torch.autograd.Function):
@@ -483,18 +487,20 @@ class HpdAux:
 # The three T-wide products of the HPD's last layer (logits, dW, dh: 3 x 2 U 128 T FLOP per training step) run on the
 # split-bf16 GEMM (csrc/linear.hip: every fp32 value split exactly into three bf16 terms, six cross products accumulated in
 # fp32; measured error against float64 equal to or below the exact-fp32 MFMA kernel's, 1.2-1.3x its speed).  False: exact
-# fp32 MFMA for these as well.
+# fp32 MFMA for these as well.  The choice travels with each call: _hpd_gemm() turns the three fields below into the GEMM_* code
+# that the stage hands to linear_fwd / linear_bwd_weight / gemm_acc; every other product of the process passes GEMM_FP32.
 # TUNING.hpd_gemm_split_bf16 (default True)
 # The logits GEMM leaves per-row (max, sum exp) partials per 64-column block in its epilogue and the row statistics + top-K come
 # out of a merge over them (1/32 of the logits' bytes) instead of a pass over the logits: one of the step's ~8.4 passes over the
 # (U, T) logit matrix less (learning mode is HBM-bound as a whole).  Needs the split-bf16 GEMM and whole 128 x 128 tiles; other
 # chunks (the ragged last one) take the separate statistics pass as before.
 # TUNING.hpd_epilogue_stats (default True)
-# Round 5: TUNING.hpd_gemm_kernel = 1 — the split GEMMs split a value once on its way into LDS (bf16 planes; 17 = the round-4 kernel);
-# TUNING.hpd_bwd_two_planes — dW and dh, which accumulate over >= 4096 terms, on two planes / three products (3 * 2^-18 |a b| per
-# product; the logits keep the exact split); TUNING.hpd_bwd_fused — the backward forms the d-logits inside the dW / dh GEMMs' loaders
-# from the logits (gngf_hpd_bwd_dot + gngf_hpd_bwd_prepare + gngf_hpd_bwd_fused) for every chunk of whole 128-row tiles; the ragged
-# last chunk of a step, L > 16 or a hidden width other than 128 take the three separate entry points.
+# Round 5: TUNING.hpd_gemm_kernel = 1 (GEMM_PLANES) — the split GEMMs split a value once on its way into LDS (bf16 planes; 17 =
+# GEMM_WAVE_SPLIT, the round-4 kernel); TUNING.hpd_bwd_two_planes — dW and dh, which accumulate over >= 4096 terms, on two planes /
+# three products (GEMM_PLANES_ACC2: 3 * 2^-18 |a b| per product; the logits keep the exact split); TUNING.hpd_bwd_fused — the backward
+# forms the d-logits inside the dW / dh GEMMs' loaders from the logits (gngf_hpd_bwd_dot + gngf_hpd_bwd_prepare + gngf_hpd_bwd_fused)
+# for every chunk of whole 128-row tiles; the ragged last chunk of a step, L > 16 or a hidden width other than 128 take the three
+# separate entry points.
 
 
 class _HpdBwdPlanes:
@@ -518,20 +524,13 @@ class _HpdBwdPlanes:
              ptr(self.Wp), ptr(self.Gtp), ptr(h), ptr(W), ptr(dW), ptr(db), ptr(dH), n, T, K, self.Hd, self.planes, stream_ptr())
 
 
-class _split_gemm:
-    """scope in which large aligned GEMMs of this process use the split-bf16 kernel (when HPD_GEMM_SPLIT_BF16)"""
-
-    def __init__(self, accumulating=False):
-        self.mode = 2 if (accumulating and TUNING.hpd_bwd_two_planes and TUNING.hpd_gemm_kernel == 1) else TUNING.hpd_gemm_kernel
-
-    def __enter__(self):
-        self.prev = query("gngf_set_gemm_split_bf16", self.mode) if TUNING.hpd_gemm_split_bf16 else None
-        return self
-
-    def __exit__(self, *exc):
-        if self.prev is not None:
-            query("gngf_set_gemm_split_bf16", self.prev)
-        return False
+def _hpd_gemm(accumulating=False):
+    """GEMM_* code of a T-wide product of the HPD's last layer (accumulating: dW / dh of the chunked backward)"""
+    if not TUNING.hpd_gemm_split_bf16:
+        return GEMM_FP32
+    if accumulating and TUNING.hpd_bwd_two_planes and TUNING.hpd_gemm_kernel == GEMM_PLANES:
+        return GEMM_PLANES_ACC2
+    return TUNING.hpd_gemm_kernel
 
 
 def _hpd_epi(n, T, K, Hd):
@@ -646,8 +645,7 @@ class HpdVertexFunction(torch.autograd.Function):
 
     @staticmethod
     def _logits(h, W, b, z):
-        with _split_gemm():
-            linear_fwd(h, W, b, ACT_NONE, y=z)
+        linear_fwd(h, W, b, ACT_NONE, y=z, gemm=_hpd_gemm())
 
     @staticmethod
     def forward(ctx, NV, vstride, K, mw, keep_probs, chunk_bytes, aux, *params):
@@ -805,9 +803,9 @@ class HpdVertexFunction(torch.autograd.Function):
                 prep.fused(dz, rowstat[s], dots[s], g_tv[s] if Kq else None, tv[s] if Kq else None, ti[s] if Kq else None,
                            h_last[s], W_last, dW, db, dH[s], u0, n, T, Kq)
             else:
-                with _split_gemm(accumulating=True):
-                    linear_bwd_weight(dz, None, h_last[s], dW, None, ACT_NONE)
-                    gemm_acc(dz, W_last, dH[s], n, Hd, T, ta=False, tb=False)     # dh = dz @ W_last, split over T
+                gemm = _hpd_gemm(accumulating=True)
+                linear_bwd_weight(dz, None, h_last[s], dW, None, ACT_NONE, gemm=gemm)
+                gemm_acc(dz, W_last, dH[s], n, Hd, T, ta=False, tb=False, gemm=gemm)     # dh = dz @ W_last, split over T
 
         def dense(u0, n, dz):              # a dense gradient on the distribution: d-logits by the dense softmax backward
             s = slice(u0, u0 + n)
@@ -821,9 +819,9 @@ class HpdVertexFunction(torch.autograd.Function):
                 p_chunk = dz
             call("gngf_softmax_bwd", ptr(p_chunk), ptr(g_tv[s] if g_tv is not None else None), ptr(ti[s]), ptr(g_probs[s]),
                  ptr(mw[s] if g_pbar is not None else None), ptr(g_pbar), L, ptr(dz), n, T, Kq, stream_ptr())
+            # this path's products as they have always run: dW exact fp32, dh on the logits' code (three planes also under hpd_bwd_two_planes)
             linear_bwd_weight(dz, None, h_last[s], dW, db, ACT_NONE)
-            with _split_gemm():
-                gemm_acc(dz, W_last, dH[s], n, Hd, T, ta=False, tb=False)
+            gemm_acc(dz, W_last, dH[s], n, Hd, T, ta=False, tb=False, gemm=_hpd_gemm())
 
         for u0 in range(0, NV, rows):
             n = min(rows, NV - u0)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNGF_ABI_VERSION 14
+#define GNGF_ABI_VERSION 15
 #define GNGF_MAX_LEVELS 32
 #define GNGF_MAX_TOPK 32
 
@@ -241,7 +241,7 @@ int gngf_encode_tiled_bwd(const float* sorted, const int32_t* items, const int32
 int gngf_vertex_grid_bwd_sorted(const void* tables, int feat_dtype, const int32_t* vert_idx, const float* vert_w, const int32_t* order,
                                 const int32_t* n_ls, const float* dG, const void* dG64, int64_t vtot, float* dtables, float* dvert_w,
                                 int Ls, int F, int64_t T, int K, int vstride, int64_t NV, void* stream);
-/* the same stage over a STATIC item list, for a frozen vertex table without d w (additive: GNGF_ABI_VERSION stays 14).  One item
+/* the same stage over a STATIC item list, for a frozen vertex table without d w (additive: no ABI version of its own).  One item
  * per (level l < Ls, vertex (gx, gy) of that level's (N_l+2)^2 grid, k < K), N of them, stably sorted by dest:
  *   item_gi = goff[l] + gy * (N_l+2) + gx  (index into the vertex grid, 0 <= gi < vtot),  item_w = vert_w[vid, k],
  *   item_dest = l * T + vert_idx[vid, k]   (0 <= dest < rows = Ls * T),                   vid = gy * vstride + gx.
@@ -252,15 +252,6 @@ int gngf_vertex_grid_bwd_sorted(const void* tables, int feat_dtype, const int32_
 int gngf_vertex_grid_bwd_flat(const int32_t* item_gi, const float* item_w, const int32_t* item_dest, int64_t N, const float* dG,
                               const void* dG64, int64_t vtot, float* dtables, int64_t rows, int F, void* stream);
 
-/* Large aligned GEMMs (full 128 x 128 tiles, contraction a multiple of 32) of the dense-layer entry points run on the
- * split-bf16 kernels while this is non-zero: every fp32 operand is split exactly into three bf16 terms and six of the nine cross
- * products are accumulated in fp32 on the bf16 matrix pipe (error <= ~2e-7 sum |a_k b_k|, at or below the rounding of an
- * fp32 fma chain; 2-2.7x the fp32-MFMA rate).  Process-wide; returns the previous setting.  Default 0 (exact fp32 MFMA).
- *   1  (any other non-zero value too): operands split once on the way into LDS, bf16 planes (round 5)
- *   2  as 1, and GEMMs that ACCUMULATE into their output (gngf_linear_bwd_weight, gngf_gemm_acc) use two planes and three
- *      products: |error| <= 3 * 2^-18 |a b| per product (the HashProbDistribution's dW / dh, contractions of >= 4096 terms)
- *   17 the round-4 kernel: every wave splits the fragments it reads (kept for A/B; same numbers as 1) */
-int gngf_set_gemm_split_bf16(int mode);
 /* gngf_decoder_bwd at in_dim == 32 with the saved hidden layers: 1 (default) = hybrid kernel — the two products with the pixel
  * on the lane (dh1 = W1^T dz2, d enc = W0^T dz1) on the bf16 pipe with the exact three-way split, the weight-gradient products
  * on the fp32 pipe; 0 = everything on the fp32 pipe.  Process-wide; returns the previous setting. */
@@ -279,17 +270,32 @@ int gngf_decoder_train(const float* enc, const float* target, const float* gloss
 /* zero_fill (optional): zero_floats floats (a multiple of 4, 16-byte aligned) cleared by this launch on the way — the table
  * gradient the encoder backward will accumulate into; the stores issue between the kernel's MFMAs (no issue time, idle HBM)
  * instead of in rider workgroups of gngf_encode_tiled_prepare. */
-/* ---- dense layers on the matrix cores (exact-fp32 MFMA).  act: 0 none, 1 ReLU, 2 LeakyReLU(0.01), 3 Sigmoid.
- * nn.Linear + activation of HashProbDistribution (models.py:80-88,105-106) and of the decoder (models.py:382-392). */
-int gngf_linear_fwd(const float* X, const float* W, const float* b, float* Y, int64_t M, int N, int K, int act, void* stream);
+/* ---- dense layers on the matrix cores.  act: 0 none, 1 ReLU, 2 LeakyReLU(0.01), 3 Sigmoid.
+ * nn.Linear + activation of HashProbDistribution (models.py:80-88,105-106) and of the decoder (models.py:382-392).
+ * gemm (gngf_linear_fwd, gngf_linear_bwd_weight, gngf_gemm_acc): which kernel THIS call's product runs on, one of the GNGF_GEMM_*
+ * codes (any other value: hipErrorInvalidValue).  The split codes split every fp32 operand exactly into three bf16 terms and
+ * accumulate six of the nine cross products in fp32 on the bf16 matrix pipe (error <= ~2e-7 sum |a_k b_k|, at or below the rounding
+ * of an fp32 fma chain; 2-2.7x the fp32-MFMA rate).  They apply to large aligned products only — whole 128 x 128 tiles, contraction
+ * (and its slice per block) a multiple of 32, 16-byte aligned operands, no activation mask on an operand, leading dimensions below
+ * 2^22; on any other shape a split code runs the exact-fp32 kernels, as GNGF_GEMM_FP32 does.  gngf_linear_bwd_input is always
+ * exact fp32, gngf_linear_fwd_rowstats always GNGF_GEMM_PLANES. */
+#define GNGF_GEMM_FP32 0         /* exact fp32 MFMA */
+#define GNGF_GEMM_PLANES 1       /* operands split once on the way into LDS: three bf16 planes (round 5) */
+#define GNGF_GEMM_PLANES_ACC2 2  /* as 1, but the entries that ACCUMULATE into their output (gngf_linear_bwd_weight, gngf_gemm_acc) use
+                                  * two planes and three products: |error| <= 3 * 2^-18 |a b| per product (the HashProbDistribution's
+                                  * dW / dh, contractions of >= 4096 terms).  gngf_linear_fwd treats it as 1. */
+#define GNGF_GEMM_WAVE_SPLIT 17  /* the round-4 kernel: every wave splits the fragments it reads (kept for A/B; same numbers as 1) */
+int gngf_linear_fwd(const float* X, const float* W, const float* b, float* Y, int64_t M, int N, int K, int act, int gemm,
+                    void* stream);
 /* dX[M,K] = (dY .* act'(Y)) W ;  Y = activated output of the layer (may be NULL when act == 0) */
 int gngf_linear_bwd_input(const float* dY, const float* Y, const float* W, float* dX, int64_t M, int N, int K, int act,
                           void* stream);
 /* dW[N,K] += (dY .* act'(Y))^T X ; db[N] += column sums.  Accumulates (float atomics): zero-fill for a fresh gradient. */
 int gngf_linear_bwd_weight(const float* dY, const float* Y, const float* X, float* dW, float* db, int64_t M, int N, int K,
-                           int act, void* stream);
+                           int act, int gemm, void* stream);
 /* C[M,N] += opA(A) opB(B), contraction Kc split over blocks.  ta: A stored (Kc,M); tb: B stored (N,Kc). */
-int gngf_gemm_acc(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kc, int ta, int tb, void* stream);
+int gngf_gemm_acc(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kc, int ta, int tb, int gemm,
+                  void* stream);
 
 /* ---- a13: the decoder MLP fused (models.py:382-392,469-470): Linear(in,64)+act, Linear(64,64)+act, Linear(64,out)+Sigmoid,
  * act = ReLU (leaky = 0) or LeakyReLU(0.01) (leaky = 1); in_dim <= 64, out_dim <= 4.  W* are (out,in) like nn.Linear. */

@@ -24,7 +24,8 @@ def test_library_exports_every_declared_symbol():
     assert len(decl) >= 8
     for name in decl:
         assert hasattr(lib, name), f"{name} declared in include/gngf.h but not exported"
-    assert lib.gngf_abi_version() == _lib.ABI_VERSION == 14
+    assert lib.gngf_abi_version() == _lib.ABI_VERSION == 15
+    assert not hasattr(lib, "gngf_set_gemm_split_bf16")      # the kernel of a GEMM is an argument of the call (ABI 15)
 
 
 def test_bindings_mirror_header_arity_and_kinds():

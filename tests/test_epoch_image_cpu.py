@@ -63,9 +63,9 @@ def test_new_entry_points_are_bound_and_abi_version_stays():
     from collision_handling_in_instantngp_amd import _lib
     for name in ("gngf_image_scatter", "gngf_image_metrics", "gngf_image_metrics_blocks", "gngf_image_metrics_workspace_words"):
         assert name in _lib.SIGNATURES, name
-    assert _lib.ABI_VERSION == 14
+    assert _lib.ABI_VERSION == 15
     lib = _lib.load()
-    assert lib.gngf_abi_version() == 14
+    assert lib.gngf_abi_version() == 15
     # the size queries launch nothing: one workgroup at least, two words per workgroup, a bounded number of workgroups
     for n in (1, 3, 4095, 4096, 4097, 3 * 2 ** 20, 2 ** 33):
         b = lib.gngf_image_metrics_blocks(n)

@@ -811,7 +811,7 @@ def test_logits_gemm_with_epilogue_statistics_equals_the_separate_pass(ops, M, T
     against gngf_linear_fwd (same split-bf16 kernel) + gngf_logits_topk_pbar, which reads every logit (reference models.py:85,
     105-116): logits bit-identical, top-K indices identical (ties -> lower index, also across blocks), probabilities and row
     statistics to fp32 rounding; NaN rows (nan_to_num: all zero, slots 0..K-1); p-bar through gngf_pbar_accumulate."""
-    from collision_handling_in_instantngp_amd._lib import call, ptr, stream_ptr, query
+    from collision_handling_in_instantngp_amd._lib import call, ptr, stream_ptr
     rng = np.random.default_rng(M + T + K)
     Kc = 128
     x = t((rng.standard_normal((M, Kc)) * 0.7).astype(np.float32))
@@ -828,11 +828,7 @@ def test_logits_gemm_with_epilogue_statistics_equals_the_separate_pass(ops, M, T
     z0 = torch.empty((M, T), device=DEV)
     z1 = torch.empty((M, T), device=DEV)
     parts = torch.empty((M, T // 64, 2), device=DEV)
-    prev = query("gngf_set_gemm_split_bf16", 1)
-    try:
-        call("gngf_linear_fwd", ptr(xx), ptr(Wt), ptr(bt), ptr(z0), M, T, Kc, 0, stream_ptr())
-    finally:
-        query("gngf_set_gemm_split_bf16", prev)
+    call("gngf_linear_fwd", ptr(xx), ptr(Wt), ptr(bt), ptr(z0), M, T, Kc, 0, 1, stream_ptr())
     call("gngf_linear_fwd_rowstats", ptr(xx), ptr(Wt), ptr(bt), ptr(z1), ptr(parts), M, T, Kc, stream_ptr())
     assert torch.equal(torch.nan_to_num(z0, nan=-7.0), torch.nan_to_num(z1, nan=-7.0))
     Lv = 5
@@ -869,7 +865,6 @@ def test_split_gemms_with_bf16_planes_in_lds(ops, mode):
     mode 2: two planes, three products, accumulating GEMMs only) against float64 and against the per-wave split kernel (mode 17):
     the three-plane kernel computes the same six terms in the same order — logits bit-identical; error over sum |a b| at the
     fp32 level for modes 1 / 17 and <= 3 * 2^-18 (its a-priori bound) for mode 2."""
-    from collision_handling_in_instantngp_amd._lib import query
     rng = np.random.default_rng(5)
     n, T, H = 512, 2048, 128
     h = t((rng.standard_normal((n, H)) * 50).astype(np.float32))
@@ -879,16 +874,12 @@ def test_split_gemms_with_bf16_planes_in_lds(ops, mode):
     dz = t((rng.standard_normal((n, T)) * np.exp(rng.uniform(-60, 0, size=(1, T)))).astype(np.float32))
 
     def run(md):
-        prev = query("gngf_set_gemm_split_bf16", md)
-        try:
-            z = ops.linear_fwd(h, W, b, ops.ACT_NONE)
-            dW = torch.zeros_like(W)
-            ops.linear_bwd_weight(dz, None, h, dW, None, ops.ACT_NONE)
-            dh = torch.zeros((n, H), device=DEV)
-            ops.gemm_acc(dz, W, dh, n, H, T, ta=False, tb=False)
-            torch.cuda.synchronize()
-        finally:
-            query("gngf_set_gemm_split_bf16", prev)
+        z = ops.linear_fwd(h, W, b, ops.ACT_NONE, gemm=md)
+        dW = torch.zeros_like(W)
+        ops.linear_bwd_weight(dz, None, h, dW, None, ops.ACT_NONE, gemm=md)
+        dh = torch.zeros((n, H), device=DEV)
+        ops.gemm_acc(dz, W, dh, n, H, T, ta=False, tb=False, gemm=md)
+        torch.cuda.synchronize()
         return z, dW, dh
 
     z, dW, dh = run(mode)
@@ -981,3 +972,79 @@ def test_softmax_backward_formed_in_the_gemm_loaders(ops, U, T, L, K, planes):
     assert query("gngf_hpd_bwd_fused_applies", U + 3, T, L, K, Hd) == 0 and query("gngf_hpd_bwd_fused_applies", U, T, 17, K, Hd) == 0
     with pytest.raises(RuntimeError):
         prep.fused(z, rowstat, dotv, dq, pk, ti32, h, W, dW, db, dH, u0, U + 3, T, K)
+
+
+# ------------------------------------------------------------------------------------------------ the GEMM kernel is chosen per call
+def _gemm_inputs(M, N, K, seed):
+    """x (M,K), w (N,K), b (N) scaled as the HPD's last layer in test_split_gemms_with_bf16_planes_in_lds"""
+    rng = np.random.default_rng(seed)
+    x = t((rng.standard_normal((M, K)) * 50).astype(np.float32))
+    w = t(((rng.random((N, K)) * 2 - 1) / K ** 0.5).astype(np.float32))
+    b = t(((rng.random(N) * 2 - 1) / K ** 0.5).astype(np.float32))
+    return x, w, b
+
+
+def test_gemm_code_is_an_argument_of_the_call(ops):
+    """(128, 128, 32), the smallest shape the split kernels take: codes 1, 2 and 17 of gngf_linear_fwd give the same bits (2 is 1 for an
+    entry that does not accumulate; 17 computes the same six terms in the same order), each within 6e-7 sum |a b| of float64, and an
+    exact-fp32 call before them equals one after them bit for bit: no call leaves anything behind for the next."""
+    x, w, b = _gemm_inputs(128, 128, 32, 11)
+    before = ops.linear_fwd(x, w, b, ops.ACT_NONE, gemm=ops.GEMM_FP32)
+    z = {g: ops.linear_fwd(x, w, b, ops.ACT_NONE, gemm=g) for g in (1, 2, 17)}
+    after = ops.linear_fwd(x, w, b, ops.ACT_NONE, gemm=ops.GEMM_FP32)
+    default = ops.linear_fwd(x, w, b, ops.ACT_NONE)
+    torch.cuda.synchronize()
+    assert torch.equal(z[1], z[2]) and torch.equal(z[1], z[17])
+    zr, sz = x.double() @ w.double().T + b.double(), x.double().abs() @ w.double().abs().T
+    for g, zg in z.items():
+        e = float(((zg.double() - zr).abs() / sz).max())
+        print(f"gemm {g}: |err| / sum|a b| {e:.2e}")
+        assert e <= 6e-7, (g, e)
+    assert torch.equal(before, after) and torch.equal(before, default)
+    assert not torch.equal(before, z[1])            # (the split codes did run another kernel: the roundings differ somewhere)
+
+
+@pytest.mark.parametrize("M,N,K", [(100, 256, 128), (130, 128, 32), (128, 128, 48), (64, 64, 16)])
+def test_split_code_on_a_shape_the_split_kernels_do_not_take_is_exact_fp32(ops, M, N, K):
+    """ragged rows below / above 128 (64-tile kernel, generic 128-tile kernel), K % 32 != 0 (fp32 fast kernel), a 64 x 64 problem:
+    every split code runs what code 0 runs — bit-identical logits"""
+    x, w, b = _gemm_inputs(M, N, K, M + N + K)
+    z0 = ops.linear_fwd(x, w, b, ops.ACT_NONE, gemm=0)
+    for g in (1, 2, 17):
+        assert torch.equal(ops.linear_fwd(x, w, b, ops.ACT_NONE, gemm=g), z0), g
+
+
+def test_accumulating_entries_take_two_planes_under_code_2_only(ops):
+    """gngf_linear_bwd_weight and gngf_gemm_acc at (M, N, Kc) = (128, 128, 4096) against float64: code 2 (two planes, three products)
+    within its a-priori 3 * 2^-18 sum |a b|, code 1 (three planes) within 6e-7 sum |a b|"""
+    rng = np.random.default_rng(7)
+    Kc = 4096
+    h = t((rng.standard_normal((Kc, 128)) * 50).astype(np.float32))
+    # gradients with 30 decades between the columns, as softmax gradients have
+    dy = t((rng.standard_normal((Kc, 128)) * np.exp(rng.uniform(-60, 0, size=(1, 128)))).astype(np.float32))
+    a = t((rng.standard_normal((128, Kc)) * np.exp(rng.uniform(-60, 0, size=(1, Kc)))).astype(np.float32))
+    W = t(((rng.random((Kc, 128)) * 2 - 1) / 128 ** 0.5).astype(np.float32))
+    dWr, sW = dy.double().T @ h.double(), dy.double().abs().T @ h.double().abs()
+    cr, sC = a.double() @ W.double(), a.double().abs() @ W.double().abs()
+    for g, tol in ((2, 3 * 2.0 ** -18), (1, 6e-7)):
+        dW, c = torch.zeros((128, 128), device=DEV), torch.zeros((128, 128), device=DEV)
+        ops.linear_bwd_weight(dy, None, h, dW, None, ops.ACT_NONE, gemm=g)
+        ops.gemm_acc(a, W, c, 128, 128, Kc, ta=False, tb=False, gemm=g)
+        torch.cuda.synchronize()
+        eW = float(((dW.double() - dWr).abs() / sW.clamp_min(1e-300)).max())
+        eC = float(((c.double() - cr).abs() / sC.clamp_min(1e-300)).max())
+        print(f"gemm {g}: |err| / sum|a b|  linear_bwd_weight {eW:.2e}  gemm_acc {eC:.2e}  (bound {tol:.2e})")
+        assert eW <= tol and eC <= tol, (g, eW, eC, tol)
+
+
+@pytest.mark.parametrize("code", [3, -1])
+def test_unknown_gemm_code_is_rejected(ops, code):
+    x, w, b = _gemm_inputs(128, 128, 32, 11)
+    c = torch.zeros((128, 128), device=DEV)
+    with pytest.raises(RuntimeError):
+        ops.linear_fwd(x, w, b, ops.ACT_NONE, gemm=code)
+    with pytest.raises(RuntimeError):
+        ops.linear_bwd_weight(x, None, x, torch.zeros((32, 32), device=DEV), None, ops.ACT_NONE, gemm=code)
+    with pytest.raises(RuntimeError):
+        ops.gemm_acc(x, w.T.contiguous(), c, 128, 128, 32, ta=False, tb=False, gemm=code)
+    torch.cuda.synchronize()

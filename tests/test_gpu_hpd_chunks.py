@@ -624,3 +624,78 @@ def test_stages_are_issued_in_the_documented_order_on_the_documented_stream(ops,
     if which == "B_first_kept":
         assert [t["kept"] for t in r.trace[:len(case.chunks)]] == [True] + [False] * (len(case.chunks) - 1)
     _check_issue_order(case, tun, mode, r.trace, log)
+
+
+# ------------------------------------------------------------------------------------------------ the kernel of every T-wide product
+GEMM_ENTRIES = ("gngf_linear_fwd", "gngf_linear_bwd_weight", "gngf_gemm_acc")       # `gemm` is their argument before the stream
+
+
+def _gemm_codes(tun):
+    """(logits, accumulating dW / dh) codes of include/gngf.h: 0 exact fp32 without hpd_gemm_split_bf16; else hpd_gemm_kernel (1 three
+    planes, 17 per wave), and 2 — two planes — for the accumulating products under hpd_bwd_two_planes with kernel 1"""
+    if not tun.hpd_gemm_split_bf16:
+        return 0, 0
+    return tun.hpd_gemm_kernel, (2 if tun.hpd_bwd_two_planes and tun.hpd_gemm_kernel == 1 else tun.hpd_gemm_kernel)
+
+
+def _logged_gemms(ops, monkeypatch, name, tun):
+    log, real_call = [], ops.call
+
+    def call(entry, *args):
+        if entry in GEMM_ENTRIES:
+            log.append((entry, args))
+        return real_call(entry, *args)
+    with monkeypatch.context() as m:
+        m.setattr(ops, "call", call)
+        run(ops, name, tun)
+    return log
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
+@pytest.mark.parametrize("kw", [dict(), dict(hpd_gemm_split_bf16=False), dict(hpd_gemm_kernel=17), dict(hpd_bwd_two_planes=False)],
+                         ids=["default", "fp32", "per_wave", "three_planes"])
+def test_every_t_wide_product_names_its_kernel(ops, monkeypatch, kw, fused):
+    """case B: the kernel of a product is an argument of its call.  Every per-chunk logits product carries the logits code, every
+    per-chunk dW / dh product the accumulating code, every hidden-layer product 0 (exact fp32)."""
+    case = CASES["B"]
+    tun = dataclasses.replace(ops.TUNING, hpd_z_cache_bytes=0, hpd_bwd_fused=fused, **kw)
+    logits, acc = _gemm_codes(tun)
+    log = _logged_gemms(ops, monkeypatch, "B", tun)
+    seen = {e: 0 for e in GEMM_ENTRIES}
+    for entry, args in log:
+        if _is_stage(entry, args, case.T):
+            seen[entry] += 1
+            assert args[-2] == (logits if entry == "gngf_linear_fwd" else acc), (entry, args[-2], logits, acc)
+        else:
+            assert args[-2] == 0, (entry, args[-2])
+    # the chunks that issue them: logits again for every chunk of the backward (+ the forward's chunks without epilogue statistics);
+    # dW and dh for the chunks the fused loaders do not take
+    want = expected_trace(case, tun)
+    n_logits = sum(1 for w in want if w["pass_"] == "bwd" or not w["epi"])
+    n_acc = sum(1 for w in want if w["pass_"] == "bwd" and not w["fused"])
+    assert n_acc >= 1 and seen == {"gngf_linear_fwd": n_logits, "gngf_linear_bwd_weight": n_acc, "gngf_gemm_acc": n_acc}, seen
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(hpd_gemm_kernel=17), dict(hpd_bwd_two_planes=False), dict(hpd_gemm_split_bf16=False)],
+                         ids=["default", "per_wave", "three_planes", "fp32"])
+def test_dense_pass_names_its_kernels(ops, monkeypatch, kw):
+    """case J (dense distribution kept, dense gradient on it): the logits and dh carry hpd_gemm_kernel — three planes also under
+    hpd_bwd_two_planes — while dW and the forward's p-bar product are exact fp32."""
+    case = CASES["J"]
+    tun = dataclasses.replace(ops.TUNING, **kw)
+    code = tun.hpd_gemm_kernel if tun.hpd_gemm_split_bf16 else 0
+    T, L, Hd, nch = case.T, case.L, case.widths[-1], len(case.chunks)
+    got = {"logits": [], "pbar": [], "dW": [], "dh": []}
+    for entry, args in _logged_gemms(ops, monkeypatch, "J", tun):
+        if entry == "gngf_linear_fwd" and args[5] == T:
+            got["logits"].append(args[-2])
+        elif entry == "gngf_linear_bwd_weight" and args[6] == T:
+            got["dW"].append(args[-2])
+        elif entry == "gngf_gemm_acc" and (args[3], args[4]) == (L, T):
+            got["pbar"].append(args[-2])
+        elif entry == "gngf_gemm_acc":
+            assert (args[4], args[5]) == (Hd, T), args[3:6]
+            got["dh"].append(args[-2])
+        else:
+            assert args[-2] == 0, (entry, args[-2])                     # hidden layers
+    assert got == {"logits": [code] * nch, "pbar": [0] * nch, "dW": [0] * nch, "dh": [code] * nch}, got

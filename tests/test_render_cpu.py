@@ -102,10 +102,10 @@ def test_entry_point_is_declared_exported_and_bound():
     from collision_handling_in_instantngp_amd import _lib, ops, train
     header = open(os.path.join(ROOT, "include", "gngf.h")).read()
     assert re.search(r"\bint\s+gngf_render\s*\(", header)
-    assert "#define GNGF_ABI_VERSION 14" in header and _lib.ABI_VERSION == 14
+    assert "#define GNGF_ABI_VERSION 15" in header and _lib.ABI_VERSION == 15
     assert len(_lib.SIGNATURES["gngf_render"]) == 28
     lib = _lib.load()
-    assert hasattr(lib, "gngf_render") and lib.gngf_abi_version() == 14
+    assert hasattr(lib, "gngf_render") and lib.gngf_abi_version() == 15
     assert callable(ops.render_lattice) and callable(train.render) and callable(train.render_psnr)
     # rejected arguments come back as hipErrorInvalidValue before anything is launched (no device needed): F = 3, rows = 0,
     # denom = 0, both outputs NULL

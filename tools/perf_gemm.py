@@ -27,7 +27,7 @@ def timeit(name, fn, flop, reps=6):
 
 
 flop = 2.0 * n * T * H
-timeit("logits", lambda: ops.call("gngf_linear_fwd", ops.ptr(h), ops.ptr(W), ops.ptr(b), ops.ptr(z), n, T, H, ops.ACT_NONE, ops.stream_ptr()), flop)
+timeit("logits", lambda: ops.call("gngf_linear_fwd", ops.ptr(h), ops.ptr(W), ops.ptr(b), ops.ptr(z), n, T, H, ops.ACT_NONE, ops.GEMM_FP32, ops.stream_ptr()), flop)
 timeit("dW", lambda: ops.linear_bwd_weight(z, None, h, dW, None, ops.ACT_NONE), flop)
 timeit("dh", lambda: ops.gemm_acc(z, W, g, n, H, T, ta=False, tb=False), flop)
 ref = (z[:64, :4096].double() @ W[:4096].double())
@@ -35,4 +35,4 @@ g.zero_(); ops.gemm_acc(z[:, :4096].contiguous(), W[:4096], g, n, H, 4096, ta=Fa
 print("dh check", float((g[:64].double() - ref).abs().max() / ref.abs().max()))
 for Hx in (32, 64, 256):
     hx = torch.randn(n, Hx, device=dev); Wx = torch.randn(T, Hx, device=dev)
-    timeit(f"logitsK{Hx}", lambda: ops.call("gngf_linear_fwd", ops.ptr(hx), ops.ptr(Wx), ops.ptr(b), ops.ptr(z), n, T, Hx, ops.ACT_NONE, ops.stream_ptr()), 2.0 * n * T * Hx)
+    timeit(f"logitsK{Hx}", lambda: ops.call("gngf_linear_fwd", ops.ptr(hx), ops.ptr(Wx), ops.ptr(b), ops.ptr(z), n, T, Hx, ops.ACT_NONE, ops.GEMM_FP32, ops.stream_ptr()), 2.0 * n * T * Hx)

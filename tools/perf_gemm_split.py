@@ -2,7 +2,7 @@
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from collision_handling_in_instantngp_amd import ops, _lib
+from collision_handling_in_instantngp_amd import ops
 dev = torch.device("cuda")
 n, T, H = 2048, 2 ** 19, 128
 g = torch.Generator(device=dev).manual_seed(1)
@@ -18,27 +18,25 @@ def timeit(fn, reps=5):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
 res = {}
-MODES = (0, 17, 1, 2)      # exact fp32 MFMA | per-wave three-way split | three bf16 planes in LDS | two planes (accumulating GEMMs)
+MODES = (0, 17, 1, 2)      # ops.GEMM_* codes: exact fp32 MFMA | per-wave three-way split | three bf16 planes in LDS | two planes (accumulating GEMMs)
 for split in MODES + MODES:
-    _lib.query("gngf_set_gemm_split_bf16", split)
-    z = ops.linear_fwd(h, W, b, ops.ACT_NONE)
-    t1 = timeit(lambda: ops.linear_fwd(h, W, b, ops.ACT_NONE))
+    z = ops.linear_fwd(h, W, b, ops.ACT_NONE, gemm=split)
+    t1 = timeit(lambda: ops.linear_fwd(h, W, b, ops.ACT_NONE, gemm=split))
     dW = torch.zeros_like(W)
-    ops.linear_bwd_weight(dz, None, h, dW, None, ops.ACT_NONE)
+    ops.linear_bwd_weight(dz, None, h, dW, None, ops.ACT_NONE, gemm=split)
     def f2():
-        ops.linear_bwd_weight(dz, None, h, dW, None, ops.ACT_NONE)
+        ops.linear_bwd_weight(dz, None, h, dW, None, ops.ACT_NONE, gemm=split)
     t2 = timeit(f2)
-    dW.zero_(); ops.linear_bwd_weight(dz, None, h, dW, None, ops.ACT_NONE)
+    dW.zero_(); ops.linear_bwd_weight(dz, None, h, dW, None, ops.ACT_NONE, gemm=split)
     dh = torch.zeros((n, H), device=dev)
-    ops.gemm_acc(dz, W, dh, n, H, T, ta=False, tb=False)
+    ops.gemm_acc(dz, W, dh, n, H, T, ta=False, tb=False, gemm=split)
     def f3():
-        ops.gemm_acc(dz, W, dh, n, H, T, ta=False, tb=False)
+        ops.gemm_acc(dz, W, dh, n, H, T, ta=False, tb=False, gemm=split)
     t3 = timeit(f3)
-    dh.zero_(); ops.gemm_acc(dz, W, dh, n, H, T, ta=False, tb=False)
+    dh.zero_(); ops.gemm_acc(dz, W, dh, n, H, T, ta=False, tb=False, gemm=split)
     res[split] = (z, dW, dh)
     fl = 2.0 * n * T * H
     print(f"split={split}: logits {t1:.3f} ms ({fl/t1/1e9:.0f} TF)  dW {t2:.3f} ms ({fl/t2/1e9:.0f} TF)  dh {t3:.3f} ms ({fl/t3/1e9:.0f} TF)")
-_lib.query("gngf_set_gemm_split_bf16", 0)
 # float64 references on a sample of rows / columns
 rows = torch.arange(0, n, 64, device=dev)
 zr = (h[rows].double() @ W.double().T + b.double())

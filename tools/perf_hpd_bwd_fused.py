@@ -4,7 +4,7 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from collision_handling_in_instantngp_amd import ops, _lib
-from collision_handling_in_instantngp_amd._lib import call, ptr, stream_ptr, query
+from collision_handling_in_instantngp_amd._lib import call, ptr, stream_ptr
 dev = torch.device("cuda")
 U, T, H, L, K = 4096, 2 ** 19, 128, 16, 4
 g = torch.Generator(device=dev).manual_seed(1)
@@ -40,10 +40,8 @@ def f_lowrank():
     call("gngf_softmax_bwd_lowrank", ptr(dz), ptr(rowstat), ptr(dq), ptr(ti32), ptr(mw), ptr(G), L, ptr(db), ptr(scratch), ptr(pk),
          U, T, K, stream_ptr())
 def f_gemms(mode):
-    prev = query("gngf_set_gemm_split_bf16", mode)
-    ops.linear_bwd_weight(dz, None, h, dW, None, ops.ACT_NONE)
-    ops.gemm_acc(dz, W, dH, U, H, T, ta=False, tb=False)
-    query("gngf_set_gemm_split_bf16", prev)
+    ops.linear_bwd_weight(dz, None, h, dW, None, ops.ACT_NONE, gemm=mode)
+    ops.gemm_acc(dz, W, dH, U, H, T, ta=False, tb=False, gemm=mode)
 for rep in range(2):
     dz.copy_(z)
     t_dot = timeit(f_dot)
