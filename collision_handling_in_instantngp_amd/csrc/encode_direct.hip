@@ -148,6 +148,101 @@ mrhe_bwd_kernel(const TT* __restrict__ tables, const int64_t* __restrict__ idx, 
   }
 }
 
+// K > GNGF_MAX_TOPK (the wide path, up to GNGF_MAX_TOPK_WIDE): the same two kernels WITHOUT per-thread K-arrays.  A first pass over the
+// instance's K probabilities leaves the blend's maximum and sum (blend_weights' loops, same order); every weight is then formed where
+// it is used, and the backward recomputes each dot_k = <g, row_k> in its last pass instead of storing it.
+struct BlendStat { float m, s; };
+__device__ __forceinline__ BlendStat blend_stat(const float* __restrict__ q, int K, int blend) {
+  BlendStat b = {0.f, 1.f};
+  if (blend == GNGF_BLEND_SOFTMAX) {
+    b.m = q[0];
+    for (int k = 1; k < K; ++k) b.m = fmaxf(b.m, q[k]);
+    b.s = 0.f;
+    for (int k = 0; k < K; ++k) b.s += expf(q[k] - b.m);
+  } else if (blend == GNGF_BLEND_NORM) {
+    b.s = 0.f;
+    for (int k = 0; k < K; ++k) b.s += q[k];
+  }
+  return b;
+}
+__device__ __forceinline__ float blend_weight_of(float q, const BlendStat& b, int blend) {
+  if (blend == GNGF_BLEND_RAW) return q;
+  if (blend == GNGF_BLEND_SOFTMAX) return expf(q - b.m) / b.s;
+  return q / b.s;
+}
+
+template <int F, typename TT>
+__global__ void __launch_bounds__(kBlock)
+mrhe_fwd_wide_kernel(const TT* __restrict__ tables, const int64_t* __restrict__ idx, const float* __restrict__ probs,
+                     float* __restrict__ out, int64_t total /* P*L*4 */, int L, int64_t T, int K, int blend) {
+  const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (gid >= total) return;
+  const int L4 = L * 4;
+  const int64_t p = gid / L4;
+  const int lv = (int)(gid - p * L4);
+  const TT* tab = tables + (int64_t)(lv >> 2) * T * F;
+  const float* q = probs + gid * K;
+  const BlendStat b = blend_stat(q, K, blend);
+  float acc[F];
+#pragma unroll
+  for (int f = 0; f < F; ++f) acc[f] = 0.f;
+  for (int k = 0; k < K; ++k) {
+    const float w = blend_weight_of(q[k], b, blend);
+    const TT* r = tab + idx[gid * K + k] * F;
+#pragma unroll
+    for (int f = 0; f < F; ++f) acc[f] += tload(r + f) * w;
+  }
+  float* o = out + p * (int64_t)F * L4 + lv;
+#pragma unroll
+  for (int f = 0; f < F; ++f) o[(int64_t)f * L4] = acc[f];
+}
+
+template <int F, typename TT>
+__global__ void __launch_bounds__(kBlock)
+mrhe_bwd_wide_kernel(const TT* __restrict__ tables, const int64_t* __restrict__ idx, const float* __restrict__ probs,
+                     const float* __restrict__ gout, float* __restrict__ dtables, float* __restrict__ dprobs,
+                     int64_t total, int L, int64_t T, int K, int blend) {
+  const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (gid >= total) return;
+  const int L4 = L * 4;
+  const int64_t p = gid / L4;
+  const int lv = (int)(gid - p * L4);
+  const TT* tab = tables + (int64_t)(lv >> 2) * T * F;
+  float* dtab = dtables + (int64_t)(lv >> 2) * T * F;
+  float g[F];
+  const float* gp = gout + p * (int64_t)F * L4 + lv;
+#pragma unroll
+  for (int f = 0; f < F; ++f) g[f] = gp[(int64_t)f * L4];
+  const float* q = probs + gid * K;
+  const BlendStat b = blend_stat(q, K, blend);
+  float wdot = 0.f, qdot = 0.f;                            // sum_k w_k dot_k (softmax), sum_k dot_k q_k (norm)
+  for (int k = 0; k < K; ++k) {
+    const float w = blend_weight_of(q[k], b, blend);
+    const int64_t row = idx[gid * K + k];
+    const TT* r = tab + row * F;
+    float dot = 0.f;
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+      dot += g[f] * tload(r + f);
+      atomicAdd(dtab + row * F + f, g[f] * w);
+    }
+    wdot += w * dot;
+    qdot += dot * q[k];
+  }
+  if (!dprobs) return;
+  const float inv = 1.0f / b.s;
+  for (int k = 0; k < K; ++k) {
+    const TT* r = tab + idx[gid * K + k] * F;
+    float dot = 0.f;
+#pragma unroll
+    for (int f = 0; f < F; ++f) dot += g[f] * tload(r + f);
+    float d = dot;
+    if (blend == GNGF_BLEND_SOFTMAX) d = blend_weight_of(q[k], b, blend) * (dot - wdot);
+    else if (blend == GNGF_BLEND_NORM) d = dot * inv - qdot * inv * inv;
+    dprobs[gid * K + k] = d;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // a12 at the module boundary: feats (P,F,L,4) -> enc (P, L*F).  One lane per (p, l).
 template <int F>
@@ -312,11 +407,17 @@ extern "C" int gngf_hash_indices(const float* xy, const int32_t* n_ls, int64_t* 
 
 extern "C" int gngf_mrhe_fwd(const void* tables, int feat_dtype, const int64_t* idx, const float* probs, float* out,
                              int64_t P, int L, int F, int64_t T, int K, int blend, void* stream) {
-  GNGF_CHECK_ARG(P >= 0 && L > 0 && L <= GNGF_MAX_LEVELS && T > 0 && K >= 0 && K <= GNGF_MAX_TOPK);
+  GNGF_CHECK_ARG(P >= 0 && L > 0 && L <= GNGF_MAX_LEVELS && T > 0 && K >= 0 && K <= GNGF_MAX_TOPK_WIDE);
   GNGF_CHECK_ARG(blend >= 0 && blend <= 2);
   if (P == 0) return 0;
   GNGF_CHECK_ARG(tables && idx && out && (K == 0 || probs));
   const int64_t total = P * L * 4;
+  if (K > GNGF_MAX_TOPK) {
+    DISPATCH_TT(feat_dtype, DISPATCH_F(F, (mrhe_fwd_wide_kernel<kF, TT><<<dim3((unsigned)ceil_div(total, kBlock)), dim3(kBlock), 0,
+                                                                         as_stream(stream)>>>(
+                                static_cast<const TT*>(tables), idx, probs, out, total, L, T, K, blend))));
+    GNGF_RETURN_LAUNCH();
+  }
   DISPATCH_TT(feat_dtype, DISPATCH_F(F, (mrhe_fwd_kernel<kF, TT><<<dim3((unsigned)ceil_div(total, kBlock)), dim3(kBlock), 0,
                                                                   as_stream(stream)>>>(
                               static_cast<const TT*>(tables), idx, probs, out, total, L, T, K, blend))));
@@ -326,11 +427,17 @@ extern "C" int gngf_mrhe_fwd(const void* tables, int feat_dtype, const int64_t* 
 extern "C" int gngf_mrhe_bwd(const void* tables, int feat_dtype, const int64_t* idx, const float* probs, const float* gout,
                              float* dtables, float* dprobs, int64_t P, int L, int F, int64_t T, int K, int blend,
                              void* stream) {
-  GNGF_CHECK_ARG(P >= 0 && L > 0 && L <= GNGF_MAX_LEVELS && T > 0 && K >= 0 && K <= GNGF_MAX_TOPK);
+  GNGF_CHECK_ARG(P >= 0 && L > 0 && L <= GNGF_MAX_LEVELS && T > 0 && K >= 0 && K <= GNGF_MAX_TOPK_WIDE);
   GNGF_CHECK_ARG(blend >= 0 && blend <= 2);
   if (P == 0) return 0;
   GNGF_CHECK_ARG(tables && idx && gout && dtables && (K == 0 || probs));
   const int64_t total = P * L * 4;
+  if (K > GNGF_MAX_TOPK) {
+    DISPATCH_TT(feat_dtype, DISPATCH_F(F, (mrhe_bwd_wide_kernel<kF, TT><<<dim3((unsigned)ceil_div(total, kBlock)), dim3(kBlock), 0,
+                                                                         as_stream(stream)>>>(
+                                static_cast<const TT*>(tables), idx, probs, gout, dtables, dprobs, total, L, T, K, blend))));
+    GNGF_RETURN_LAUNCH();
+  }
   DISPATCH_TT(feat_dtype, DISPATCH_F(F, (mrhe_bwd_kernel<kF, TT><<<dim3((unsigned)ceil_div(total, kBlock)), dim3(kBlock), 0,
                                                                   as_stream(stream)>>>(
                               static_cast<const TT*>(tables), idx, probs, gout, dtables, dprobs, total, L, T, K, blend))));
@@ -376,7 +483,7 @@ extern "C" int gngf_encode_fwd(const float* xy, const void* tables_v, int feat_d
                       reinterpret_cast<const float2*>(xy), static_cast<const TT*>(tables_v), nullptr, nullptr, n_ls, enc, total, L, l0,
                       nl, T, 0, 0, 0, pow2, order))));
   } else {
-    GNGF_CHECK_ARG(vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0);
+    GNGF_CHECK_ARG(vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0);
     DISPATCH_TT(feat_dtype, DISPATCH_F(F, (encode_fwd_kernel<kF, true, TT><<<grid, block, 0, as_stream(stream)>>>(
                       reinterpret_cast<const float2*>(xy), static_cast<const TT*>(tables_v), vert_idx, vert_w, n_ls, enc, total, L,
                       l0, nl, T, K, vstride, NV, pow2, order))));
@@ -401,7 +508,7 @@ extern "C" int gngf_encode_bwd(const float* xy, const void* tables_v, int feat_d
                       reinterpret_cast<const float2*>(xy), static_cast<const TT*>(tables_v), nullptr, nullptr, n_ls, genc, dtables,
                       nullptr, total, L, l0, nl, T, 0, 0, 0, pow2))));
   } else {
-    GNGF_CHECK_ARG(vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0);
+    GNGF_CHECK_ARG(vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0);
     DISPATCH_TT(feat_dtype, DISPATCH_F(F, (encode_bwd_kernel<kF, true, TT><<<grid, block, 0, as_stream(stream)>>>(
                       reinterpret_cast<const float2*>(xy), static_cast<const TT*>(tables_v), vert_idx, vert_w, n_ls, genc, dtables,
                       dvert_w, total, L, l0, nl, T, K, vstride, NV, pow2))));

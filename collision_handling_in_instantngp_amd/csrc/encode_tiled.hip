@@ -2090,7 +2090,7 @@ extern "C" int gngf_encode_tiled_prepare(const float* xy, int64_t P, int tile_sh
   // G == NULL (spatial-hash source only): no vertex grid is wanted — the pixel stage gathers from the level tables itself
   // (gngf_encode_tiled_fwd_fused) — and the riders only clear (dG_zero / clear_rows), or do not run at all
   GNGF_CHECK_ARG(Ls > 0 && Ls <= GNGF_MAX_LEVELS && T > 0 && tables && n_ls && n_ls_host && (G || mode == GNGF_MODE_HASH));
-  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0));
+  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0));
   GNGF_CHECK_ARG(zero_fill_ok(zero_fill, zero_floats));
   const int64_t nvec = zero_fill ? zero_floats / 4 : 0;
   const int zblocks = zero_fill_blocks(nvec);
@@ -2145,7 +2145,7 @@ extern "C" int gngf_vertex_grid_fwd(const void* tables, int feat_dtype, const in
                                     const int32_t* n_ls_host, float* G, int Ls, int F, int64_t T, int K, int mode,
                                     int vstride, int64_t NV, void* stream) {
   GNGF_CHECK_ARG(Ls > 0 && Ls <= GNGF_MAX_LEVELS && T > 0 && tables && n_ls && n_ls_host && G);
-  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0));
+  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0));
   const int side = max_grid_side(n_ls_host, Ls);
   dim3 grid((unsigned)ceil_div((int64_t)side * side, 256), (unsigned)Ls), block(256);
   const bool pow2 = (T & (T - 1)) == 0;
@@ -2164,7 +2164,7 @@ extern "C" int gngf_vertex_grid_bwd(const void* tables, int feat_dtype, const in
                                     const int32_t* n_ls_host, const float* dG, float* dtables, float* dvert_w, int Ls, int F,
                                     int64_t T, int K, int mode, int vstride, int64_t NV, void* stream) {
   GNGF_CHECK_ARG(Ls > 0 && Ls <= GNGF_MAX_LEVELS && T > 0 && tables && n_ls && n_ls_host && dG && dtables);
-  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0));
+  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0));
   int64_t vtot = 0;
   for (int l = 0; l < Ls; ++l) vtot += (int64_t)(n_ls_host[l] + 2) * (n_ls_host[l] + 2);
   dim3 grid((unsigned)ceil_div(vtot, 256)), block(256);
@@ -2304,7 +2304,7 @@ extern "C" int gngf_encode_tiled_fwd_fused(const float* sorted, const int32_t* i
   GNGF_CHECK_ARG(!next_count || bin_job_dev(next_count, true, &cride));
   if (max_items == 0 && !next_count) return 0;
   GNGF_CHECK_ARG(sorted && items && n_items && n_ls && n_ls_host && tables && enc && T > 0);
-  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0));
+  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0));
   if (!interleaved_applies(n_ls_host, Ls, F, tile_shift, lds_bytes / 4, false)) {
     // generic pixel-stage kernel (shapes whose level-interleaved image does not fit, F != 2): spatial-hash source, fp32 or fp16 tables
     GNGF_CHECK_ARG(mode == GNGF_MODE_HASH && !next_count);
@@ -2471,7 +2471,7 @@ extern "C" int gngf_vertex_grid_bwd_sorted(const void* tables, int feat_dtype, c
                                            const int32_t* order, const int32_t* n_ls, const float* dG, const void* dG64,
                                            int64_t vtot, float* dtables, float* dvert_w, int Ls, int F, int64_t T, int K,
                                            int vstride, int64_t NV, void* stream) {
-  GNGF_CHECK_ARG(Ls > 0 && Ls <= GNGF_MAX_LEVELS && T > 0 && K > 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0);
+  GNGF_CHECK_ARG(Ls > 0 && Ls <= GNGF_MAX_LEVELS && T > 0 && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0);
   GNGF_CHECK_ARG(tables && vert_idx && vert_w && order && n_ls && (dG || (dG64 && vtot > 0)) && dtables && NV * K < (1ll << 31));
   const int64_t NE = NV * K;
   if (dG64) {

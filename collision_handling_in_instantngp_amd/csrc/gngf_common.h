@@ -178,4 +178,9 @@ __device__ __forceinline__ void decoder_reduce_block(int blk, const float* __res
   else db2[e - o4] = s;
 }
 
+// The wide-K path (csrc/topk_wide.hip), K in (GNGF_MAX_TOPK, GNGF_MAX_TOPK_WIDE]: the entry points of hpd.hip dispatch to these.
+// mode: 0 in-place softmax + top-K, 1 streaming statistics + top-K (z only read), 2 top-K of raw rows (z only read).
+int wide_topk_launch(int mode, float* z, float* topv, int32_t* topi, float* rowstat, int64_t U, int64_t T, int K, hipStream_t s);
+int wide_blend_launch(bool bwd, const float* q, const float* dw, float* out, int64_t U, int K, int blend, hipStream_t s);
+
 }  // namespace gngf

@@ -118,12 +118,13 @@ softmax_topk_kernel(float* __restrict__ z, float* __restrict__ topv, int32_t* __
 //   g_t = gdense[row,t] (optional) + sum_l mw[row,l] * G[l,t] (optional)  [+ dq_k at t = topi_k]
 //   dz_t = p_t * (g_t - sum_t' p_t' g_t')          (p = post-nan_to_num probabilities: NaN rows have p = 0 -> dz = 0)
 // dz may alias p (in place).
+template <int KMAX>
 __global__ void __launch_bounds__(kRowBlock)
 softmax_bwd_kernel(const float* __restrict__ P, const float* __restrict__ dq, const int32_t* __restrict__ topi,
                    const float* __restrict__ gdense, const float* __restrict__ mw, const float* __restrict__ G, int L,
                    float* __restrict__ dZ, int64_t T, int K) {
   __shared__ float red[4];
-  __shared__ float pk[GNGF_MAX_TOPK];
+  __shared__ float pk[KMAX];
   __shared__ float mwl[GNGF_MAX_LEVELS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t row = blockIdx.x;
@@ -869,9 +870,10 @@ using namespace gngf;
 
 extern "C" int gngf_softmax_topk(float* logits_probs, float* topk_val, int32_t* topk_idx, float* rowstat, int64_t U, int64_t T,
                                  int K, void* stream) {
-  GNGF_CHECK_ARG(U >= 0 && T > 0 && K > 0 && K <= GNGF_MAX_TOPK && K <= T && T < INT_MAX);
+  GNGF_CHECK_ARG(U >= 0 && T > 0 && K > 0 && K <= GNGF_MAX_TOPK_WIDE && K <= T && T < INT_MAX);
   if (U == 0) return 0;
   GNGF_CHECK_ARG(logits_probs && topk_val && topk_idx);
+  if (K > GNGF_MAX_TOPK) return wide_topk_launch(0, logits_probs, topk_val, topk_idx, rowstat, U, T, K, as_stream(stream));
   const size_t smem = ((size_t)2 * K * kRowBlock + 16) * sizeof(float);
   if (smem > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(softmax_topk_kernel),
@@ -889,10 +891,15 @@ static int launch_pbar(const float* logits, const float* rowstat, const float* m
 
 extern "C" int gngf_logits_topk_pbar(const float* logits, float* topk_val, int32_t* topk_idx, float* rowstat, const float* mw,
                                      int L, float* pbar, int64_t U, int64_t T, int K, void* stream) {
-  GNGF_CHECK_ARG(U >= 0 && T > 0 && K > 0 && K <= GNGF_MAX_TOPK && K <= T && T < INT_MAX && L >= 0 && L <= GNGF_MAX_LEVELS);
+  GNGF_CHECK_ARG(U >= 0 && T > 0 && K > 0 && K <= GNGF_MAX_TOPK_WIDE && K <= T && T < INT_MAX && L >= 0 && L <= GNGF_MAX_LEVELS);
   if (U == 0) return 0;
   GNGF_CHECK_ARG(logits && topk_val && topk_idx && rowstat && (L == 0 || (mw && pbar)));
   hipStream_t s = as_stream(stream);
+  if (K > GNGF_MAX_TOPK) {
+    const int e = wide_topk_launch(1, const_cast<float*>(logits), topk_val, topk_idx, rowstat, U, T, K, s);
+    if (e != 0 || L == 0) return e;
+    return launch_pbar(logits, rowstat, mw, L, pbar, U, T, s);
+  }
   const size_t smem = ((size_t)2 * K * kRowBlock + 16) * sizeof(float);
   if (smem > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(logits_stats_topk_kernel),
@@ -941,9 +948,10 @@ extern "C" int gngf_pbar_accumulate(const float* logits, const float* rowstat, c
 
 // DifferentiableTopk.forward alone (models.py:11): top-K of arbitrary rows, values sorted descending, ties -> lower index.
 extern "C" int gngf_topk(const float* x, float* topk_val, int32_t* topk_idx, int64_t U, int64_t T, int K, void* stream) {
-  GNGF_CHECK_ARG(U >= 0 && T > 0 && K > 0 && K <= GNGF_MAX_TOPK && K <= T && T < INT_MAX);
+  GNGF_CHECK_ARG(U >= 0 && T > 0 && K > 0 && K <= GNGF_MAX_TOPK_WIDE && K <= T && T < INT_MAX);
   if (U == 0) return 0;
   GNGF_CHECK_ARG(x && topk_val && topk_idx);
+  if (K > GNGF_MAX_TOPK) return wide_topk_launch(2, const_cast<float*>(x), topk_val, topk_idx, nullptr, U, T, K, as_stream(stream));
   const size_t smem = ((size_t)2 * K * kRowBlock + 16) * sizeof(float);
   if (smem > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(softmax_topk_kernel),
@@ -958,11 +966,15 @@ extern "C" int gngf_topk(const float* x, float* topk_val, int32_t* topk_idx, int
 extern "C" int gngf_softmax_bwd(const float* probs, const float* dq, const int32_t* topk_idx, const float* gdense,
                                 const float* mw, const float* G, int L, float* dlogits, int64_t U, int64_t T, int K,
                                 void* stream) {
-  GNGF_CHECK_ARG(U >= 0 && T > 0 && K >= 0 && K <= GNGF_MAX_TOPK && L >= 0 && L <= GNGF_MAX_LEVELS);
+  GNGF_CHECK_ARG(U >= 0 && T > 0 && K >= 0 && K <= GNGF_MAX_TOPK_WIDE && L >= 0 && L <= GNGF_MAX_LEVELS);
   if (U == 0) return 0;
   GNGF_CHECK_ARG(probs && dlogits && (K == 0 || topk_idx) && ((mw == nullptr) == (G == nullptr)));
-  softmax_bwd_kernel<<<dim3((unsigned)U), dim3(kRowBlock), 0, as_stream(stream)>>>(probs, dq, topk_idx, gdense, mw, G, L,
-                                                                                    dlogits, T, K);
+  if (K <= GNGF_MAX_TOPK)
+    softmax_bwd_kernel<GNGF_MAX_TOPK><<<dim3((unsigned)U), dim3(kRowBlock), 0, as_stream(stream)>>>(probs, dq, topk_idx, gdense, mw, G,
+                                                                                                     L, dlogits, T, K);
+  else
+    softmax_bwd_kernel<GNGF_MAX_TOPK_WIDE><<<dim3((unsigned)U), dim3(kRowBlock), 0, as_stream(stream)>>>(probs, dq, topk_idx, gdense,
+                                                                                                          mw, G, L, dlogits, T, K);
   GNGF_RETURN_LAUNCH();
 }
 
@@ -972,7 +984,7 @@ extern "C" int gngf_softmax_bwd(const float* probs, const float* dq, const int32
 extern "C" int gngf_softmax_bwd_lowrank(float* logits_dz, const float* rowstat, const float* dq, const int32_t* topk_idx,
                                         const float* mw, const float* G, int L, float* db, float* scratch, const float* topk_p,
                                         int64_t U, int64_t T, int K, void* stream) {
-  GNGF_CHECK_ARG(U >= 0 && T > 0 && K >= 0 && K <= GNGF_MAX_TOPK && L >= 0 && L <= GNGF_MAX_LEVELS);
+  GNGF_CHECK_ARG(U >= 0 && T > 0 && K >= 0 && K <= GNGF_MAX_TOPK_WIDE && L >= 0 && L <= GNGF_MAX_LEVELS);
   if (U == 0) return 0;
   GNGF_CHECK_ARG(logits_dz && rowstat && scratch && (K == 0 || (dq && topk_idx)) && (L == 0 || (mw && G)));
   hipStream_t s = as_stream(stream);
@@ -1018,7 +1030,7 @@ extern "C" int gngf_softmax_bwd_lowrank(float* logits_dz, const float* rowstat, 
 //   dot[r] = sum_k topk_p[r,k] dq[r,k] + sum_t p[r,t] (mw G)[r,t]          one read of the logits, nothing written but dot (U)
 extern "C" int gngf_hpd_bwd_dot(const float* logits, const float* rowstat, const float* dq, const float* topk_p, const float* mw,
                                 const float* G, int L, float* dot, int64_t U, int64_t T, int K, void* stream) {
-  GNGF_CHECK_ARG(U >= 0 && T > 0 && T % 32 == 0 && T < (1 << 24) && K >= 0 && K <= GNGF_MAX_TOPK && L >= 0 && L <= 32);
+  GNGF_CHECK_ARG(U >= 0 && T > 0 && T % 32 == 0 && T < (1 << 24) && K >= 0 && K <= GNGF_MAX_TOPK_WIDE && L >= 0 && L <= 32);
   if (U == 0) return 0;
   GNGF_CHECK_ARG(logits && rowstat && dot && (K == 0 || (dq && topk_p)) && (L == 0 || (mw && G)));
   hipStream_t s = as_stream(stream);
@@ -1048,17 +1060,19 @@ extern "C" int gngf_vertex_coords(float* verts, int64_t u0, int64_t count, int v
 }
 
 extern "C" int gngf_blend_fwd(const float* q, float* w, int64_t U, int K, int blend, void* stream) {
-  GNGF_CHECK_ARG(U >= 0 && K > 0 && K <= GNGF_MAX_TOPK && blend >= 0 && blend <= 2);
+  GNGF_CHECK_ARG(U >= 0 && K > 0 && K <= GNGF_MAX_TOPK_WIDE && blend >= 0 && blend <= 2);
   if (U == 0) return 0;
   GNGF_CHECK_ARG(q && w);
+  if (K > GNGF_MAX_TOPK) return wide_blend_launch(false, q, nullptr, w, U, K, blend, as_stream(stream));
   blend_fwd_kernel<<<dim3((unsigned)ceil_div(U, 256)), dim3(256), 0, as_stream(stream)>>>(q, w, U, K, blend);
   GNGF_RETURN_LAUNCH();
 }
 
 extern "C" int gngf_blend_bwd(const float* q, const float* dw, float* dq, int64_t U, int K, int blend, void* stream) {
-  GNGF_CHECK_ARG(U >= 0 && K > 0 && K <= GNGF_MAX_TOPK && blend >= 0 && blend <= 2);
+  GNGF_CHECK_ARG(U >= 0 && K > 0 && K <= GNGF_MAX_TOPK_WIDE && blend >= 0 && blend <= 2);
   if (U == 0) return 0;
   GNGF_CHECK_ARG(q && dw && dq);
+  if (K > GNGF_MAX_TOPK) return wide_blend_launch(true, q, dw, dq, U, K, blend, as_stream(stream));
   blend_bwd_kernel<<<dim3((unsigned)ceil_div(U, 256)), dim3(256), 0, as_stream(stream)>>>(q, dw, dq, U, K, blend);
   GNGF_RETURN_LAUNCH();
 }
@@ -1085,7 +1099,7 @@ extern "C" int gngf_multiplicity_weights(const int32_t* counts, float* mw, int64
 extern "C" int gngf_expand_vertex_table(const float* xy, const int32_t* n_ls, const int32_t* src_idx, const float* src_val,
                                         int64_t* vid_out, int64_t* out_idx, float* out_val, int64_t P, int L, int K,
                                         int vstride, int64_t NV, void* stream) {
-  GNGF_CHECK_ARG(P >= 0 && L > 0 && L <= GNGF_MAX_LEVELS && K >= 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0);
+  GNGF_CHECK_ARG(P >= 0 && L > 0 && L <= GNGF_MAX_LEVELS && K >= 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0);
   if (P == 0) return 0;
   GNGF_CHECK_ARG(xy && n_ls && (!out_idx || src_idx) && (!out_val || src_val));
   const int64_t total = P * L * 4;

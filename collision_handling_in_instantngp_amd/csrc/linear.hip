@@ -1324,7 +1324,7 @@ extern "C" int gngf_gemm_acc(const float* A, const float* B, float* C, int64_t M
 
 // Does gngf_hpd_bwd_fused take this shape?  (whole 128-row / 128-column tiles, last hidden width 128, L <= 16, 32-bit windows)
 extern "C" int gngf_hpd_bwd_fused_applies(int64_t U, int64_t T, int L, int K, int hidden) {
-  return (U > 0 && U % 128 == 0 && T % 128 == 0 && T < (1 << 22) && hidden == 128 && L >= 0 && L <= 16 && K >= 0 && K <= GNGF_MAX_TOPK) ? 1 : 0;
+  return (U > 0 && U % 128 == 0 && T % 128 == 0 && T < (1 << 22) && hidden == 128 && L >= 0 && L <= 16 && K >= 0 && K <= GNGF_MAX_TOPK_WIDE) ? 1 : 0;
 }
 
 // The small operands of gngf_hpd_bwd_fused, split once per backward pass into bf16 planes (planes = 2 or 3 for h and W; always the

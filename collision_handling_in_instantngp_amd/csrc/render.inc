@@ -339,7 +339,7 @@ extern "C" int gngf_render(const void* tables, int feat_dtype, const int32_t* ve
   GNGF_CHECK_ARG(tables && n_ls && W0 && b0 && W1 && b1 && W2 && b2 && (rgb || img));
   GNGF_CHECK_ARG((reinterpret_cast<uintptr_t>(tables) & 15) == 0);
   const bool vt = mode == GNGF_MODE_VERTEX_TABLE;
-  if (vt) GNGF_CHECK_ARG(vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK && vstride > 0 && NV > 0 && NV * K < ((int64_t)1 << 31));
+  if (vt) GNGF_CHECK_ARG(vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0 && NV * K < ((int64_t)1 << 31));
   RenderArgs a;
   a.tables = tables; a.vert_idx = vert_idx; a.vert_w = vert_w; a.n_ls = n_ls;
   a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2;

@@ -142,7 +142,7 @@ using namespace gngf;
 // rows that can receive a non-zero gradient as long as coordinates lie in [0,1]^2.
 extern "C" int gngf_mark_reachable_rows(const int32_t* n_ls, const int32_t* n_ls_host, int L, const int32_t* vert_idx, int K,
                                         int64_t T, int vstride, int64_t NV, uint32_t* rowmask, void* stream) {
-  GNGF_CHECK_ARG(L > 0 && L <= GNGF_MAX_LEVELS && K > 0 && K <= GNGF_MAX_TOPK && T > 0 && n_ls && n_ls_host && rowmask);
+  GNGF_CHECK_ARG(L > 0 && L <= GNGF_MAX_LEVELS && K > 0 && K <= GNGF_MAX_TOPK_WIDE && T > 0 && n_ls && n_ls_host && rowmask);
   GNGF_CHECK_ARG(vert_idx ? (vstride > 0 && NV > 0) : K == 1);
   int64_t total = 0;
   for (int l = 0; l < L; ++l) {
@@ -161,7 +161,7 @@ extern "C" int gngf_mark_reachable_rows(const int32_t* n_ls, const int32_t* n_ls
 // = what gngf_distinct_slot_counts sees in the (P,L,4[,K]) index tensor of the same batch (models.py:568-619), without it.
 extern "C" int gngf_mark_batch_slots(const float* xy, const int32_t* n_ls, int64_t P, int L, const int32_t* vert_idx, int K,
                                      int64_t T, int vstride, int64_t NV, uint32_t* touched, uint32_t* bitmap, void* stream) {
-  GNGF_CHECK_ARG(P >= 0 && L > 0 && L <= GNGF_MAX_LEVELS && K > 0 && K <= GNGF_MAX_TOPK && T > 0 && vstride > 0 && NV > 0 && touched && bitmap);
+  GNGF_CHECK_ARG(P >= 0 && L > 0 && L <= GNGF_MAX_LEVELS && K > 0 && K <= GNGF_MAX_TOPK_WIDE && T > 0 && vstride > 0 && NV > 0 && touched && bitmap);
   GNGF_CHECK_ARG(vert_idx || K == 1);
   if (P == 0) return 0;
   GNGF_CHECK_ARG(xy && n_ls);

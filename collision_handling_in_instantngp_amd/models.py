@@ -47,6 +47,7 @@ class DifferentiableTopk(torch.autograd.Function):
     def forward(ctx, input: torch.Tensor, k: int, dim: int):
         if dim not in (-1, input.dim() - 1):
             raise ValueError("DifferentiableTopk: only the last dimension is supported")
+        k = ops.check_topk(k)
         x = input.reshape(-1, input.shape[-1]).contiguous()
         U, T = x.shape
         vals = torch.empty((U, k), dtype=torch.float32, device=x.device)

@@ -14,6 +14,16 @@ from ._lib import call, ptr, query, stream_ptr
 
 BLEND_CODES = {True: 0, None: 1, False: 2}   # should_softmax_topk_features -> GNGF_BLEND_*
 MODE_HASH, MODE_VERTEX_TABLE = 0, 1
+MAX_TOPK = 128        # GNGF_MAX_TOPK_WIDE: the largest K any entry point takes
+MAX_TOPK_LIST = 32    # GNGF_MAX_TOPK: above it the selection, blend and module-boundary kernels are those of csrc/topk_wide.hip
+
+
+def check_topk(K):
+    """K of a call into the library: ValueError (naming the limit) instead of the library's hipErrorInvalidValue"""
+    K = int(K)
+    if K > MAX_TOPK:
+        raise ValueError(f"topk_k = {K} exceeds the limit of {MAX_TOPK} (ops.MAX_TOPK, GNGF_MAX_TOPK_WIDE)")
+    return K
 
 _f32, _i32, _i64 = torch.float32, torch.int32, torch.int64
 
@@ -183,7 +193,7 @@ class MrheFunction(torch.autograd.Function):
         tables, idx = _c(tables), _c(idx)
         L, T, F = tables.shape
         P = idx.shape[0]
-        K = 0 if idx.dim() == 3 else idx.shape[-1]
+        K = check_topk(0 if idx.dim() == 3 else idx.shape[-1])
         if K:
             probs = _c(probs)
         out = torch.empty((P, F, L, 4), dtype=_f32, device=tables.device)
@@ -342,7 +352,7 @@ class EncodeDirectFunction(torch.autograd.Function):
         L, T, F = tables.shape
         P = xy.shape[0]
         mode = MODE_HASH if vert_idx is None else MODE_VERTEX_TABLE
-        K = 0 if vert_idx is None else vert_idx.shape[1]
+        K = check_topk(0 if vert_idx is None else vert_idx.shape[1])
         NV = 0 if vert_idx is None else vert_idx.shape[0]
         enc = torch.empty((P, L * F), dtype=_f32, device=tables.device)
         call("gngf_encode_fwd", ptr(xy, _f32, "xy"), *_tab(tables), ptr(vert_idx, _i32, "vert_idx"),
@@ -454,7 +464,7 @@ def expand_vertex_table(xy, n_ls, vstride, NV, src_idx=None, src_val=None, want_
     """(P,L,4[,K]) reference-shaped tensors from per-vertex (NV,K) tables (reference return contract models.py:478-484)."""
     xy = _c(xy)
     P, L = xy.shape[0], n_ls.numel()
-    K = src_idx.shape[1] if src_idx is not None else (src_val.shape[1] if src_val is not None else 0)
+    K = check_topk(src_idx.shape[1] if src_idx is not None else (src_val.shape[1] if src_val is not None else 0))
     dev = xy.device
     vid = torch.empty((P, L, 4), dtype=_i64, device=dev) if want_vid else None
     oi = torch.empty((P, L, 4, K), dtype=_i64, device=dev) if src_idx is not None else None
@@ -536,7 +546,7 @@ def _hpd_gemm(accumulating=False):
 def _hpd_epi(n, T, K, Hd):
     """forward, per chunk: row statistics in the logits GEMM's epilogue — whole 128 x 128 tiles on the split-bf16 kernel"""
     return (TUNING.hpd_epilogue_stats and TUNING.hpd_gemm_split_bf16 and n % 128 == 0 and T % 128 == 0 and Hd % 32 == 0
-            and K * 64 <= T and T < (1 << 22))
+            and K * 64 <= T and K <= MAX_TOPK_LIST and T < (1 << 22))     # (gngf_rowstats_topk: the per-thread-list selection)
 
 
 def _hpd_fused(n, T, Lq, Kq, Hd):
@@ -649,6 +659,7 @@ class HpdVertexFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, NV, vstride, K, mw, keep_probs, chunk_bytes, aux, *params):
+        K = check_topk(K)
         params = tuple(_c(p) for p in params)
         n_layers = len(params) // 2
         W_last, b_last = params[-2], params[-1]
@@ -854,6 +865,7 @@ class BlendFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, blend_code):
         q = _c(q)
+        check_topk(q.shape[1])
         w = torch.empty_like(q)
         call("gngf_blend_fwd", ptr(q, _f32), ptr(w), q.shape[0], q.shape[1], blend_code, stream_ptr())
         ctx.save_for_backward(q)
@@ -875,6 +887,7 @@ class SoftmaxTopkFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, K):
+        K = check_topk(K)
         probs = logits.detach().clone().contiguous()
         U, T = probs.shape
         tv = torch.empty((U, K), dtype=_f32, device=probs.device)
@@ -1626,7 +1639,7 @@ class EncodeFunction(torch.autograd.Function):
         L, T, F = tables.shape
         P = xy.shape[0]
         mode = MODE_HASH if vert_idx is None else MODE_VERTEX_TABLE
-        K = 0 if vert_idx is None else vert_idx.shape[1]
+        K = check_topk(0 if vert_idx is None else vert_idx.shape[1])
         NV = 0 if vert_idx is None else vert_idx.shape[0]
         enc = torch.empty((P, L * F), dtype=_f32, device=tables.device)
         ws = None
@@ -2014,9 +2027,9 @@ def render_lattice(tables, n_ls, decoder_params, rows, cols, denom, origin=(0, 0
     for name, t in (("out_rgb", out_rgb), ("out_image", out_image)):
         if t is not None and t.numel() != rows * cols * C:
             raise ValueError(f"{name} holds {t.numel()} elements for a {rows} x {cols} x {C} render")
-    tp, code = _tab(tables)
     vt = vert_idx is not None
-    K = int(vert_idx.shape[1]) if vt else 0
+    K = check_topk(vert_idx.shape[1]) if vt else 0
+    tp, code = _tab(tables)
     NV = int(vert_idx.shape[0]) if vt else 0
     if vt and tuple(vert_w.shape) != (NV, K):
         raise ValueError(f"vert_w must be (NV, K) = ({NV}, {K}), got {tuple(vert_w.shape)}")
@@ -2284,7 +2297,7 @@ def encode_kernels(xy, n_ls, n_ls_host, tables, vert_idx, vert_w, vstride, genc,
     L, T, F = tables.shape
     P = xy.shape[0]
     mode = MODE_HASH if vert_idx is None else MODE_VERTEX_TABLE
-    K = 0 if vert_idx is None else vert_idx.shape[1]
+    K = check_topk(0 if vert_idx is None else vert_idx.shape[1])
     NV = 0 if vert_idx is None else vert_idx.shape[0]
     enc = torch.empty((P, L * F), dtype=_f32, device=xy.device)
     dtables = _grad_buffer(tables)

@@ -31,7 +31,8 @@ extern "C" {
 
 #define GNGF_ABI_VERSION 15
 #define GNGF_MAX_LEVELS 32
-#define GNGF_MAX_TOPK 32
+#define GNGF_MAX_TOPK 32        /* the bound of the per-thread-list kernels; larger K takes the wide path */
+#define GNGF_MAX_TOPK_WIDE 128  /* the largest K any entry point accepts (csrc/topk_wide.hip) */
 
 /* blend of the K looked-up rows — models.py:212-217 (global should_softmax_topk_features) */
 enum { GNGF_BLEND_SOFTMAX = 0 /* True */, GNGF_BLEND_RAW = 1 /* None */, GNGF_BLEND_NORM = 2 /* False */ };
