@@ -97,6 +97,7 @@ SIGNATURES = {
     "gngf_image_metrics_workspace_words": [_L],
     "gngf_image_metrics": [_P, _P, _P, _P, _L, _P],
     "gngf_render": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _F, _I, _I, _L, _I, _I, _I, _L, _I, _I, _P],
+    "gngf_render_grid": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _F, _I, _I, _I, _I, _P],
     "gngf_epoch_state_bytes": [],
     "gngf_epoch_log_int_columns": [_I, _I],
     "gngf_epoch_tail": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _D, _D, _I, _L, _P],

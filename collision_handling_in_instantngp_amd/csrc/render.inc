@@ -15,11 +15,16 @@
 // Hash source: the loads of a group are in flight under the 64 MFMAs that follow them.  Vertex-table source: the row index
 // depends on a load, so a group's K rows are accumulated where the group is issued (levels in chunks of <= 8 corners, the
 // next k's index / weight pairs requested while the rows of k arrive).
+// Grid source (gngf_render_grid): a baked model — the vertex grid of every level as the vertex stage writes it (G of
+// gngf_vertex_grid_fwd with Ls = L).  A corner is row goff_l + gy (N_l + 2) + gx of it, gx / gy clamped to the level's grid:
+// four independent dense loads a level, issued where the hash source issues its rows — no hash, no table, no index loads.
+// It holds fewer live values than the other sources: no scratch at 32 features, 8 / 72 spilled registers at 64 (exact / narrower).
 // Registers: the 32-feature forms fit the 512-entry file; the 64-feature forms (64 more weight registers, two groups) spill
 // 28 - 125 registers to scratch in the gather phases.
 namespace gngf {
 
 constexpr int kRenderCols = 16, kRenderRows = 8;        // the workgroup's block; a wave renders 8 x 4 of it
+constexpr int kSrcHash = 0, kSrcTable = 1, kSrcGrid = 2;  // where a corner's features come from
 
 struct RenderArgs {
   const void* tables; const int32_t* vert_idx; const float* vert_w; const int32_t* n_ls;
@@ -34,6 +39,11 @@ struct RenderArgs {
   int out_dim;
   bool pow2;
 };
+// the grid source's own arguments (a second kernel argument: the other sources' launches carry an empty one)
+struct RenderGridArgs { const float* grid; int64_t goff[GNGF_MAX_LEVELS]; };
+struct RenderNoGrid {};
+template <int SRC> struct RenderSrcArgs { using type = RenderNoGrid; };
+template <> struct RenderSrcArgs<kSrcGrid> { using type = RenderGridArgs; };
 
 // one table row (F consecutive values, F sizeof(TT)-aligned: the table base is 16-byte aligned) as fp32 — tload's values
 template <int F> __device__ __forceinline__ void row_load(const float* r, float (&o)[F]) {
@@ -61,11 +71,35 @@ __device__ __forceinline__ Cell scaled_cell(float x, float y, int n, float& sx, 
 }
 
 // Levels lev0 .. lev0 + 16 / F - 1 at coordinate (x, y).  Levels >= L (the narrower forms) give zeros.
-template <int F, bool VT, bool EXACT, typename TT>
-__device__ __forceinline__ void render_issue(RenderGroup& G, const RenderArgs& a, int lev0, float x, float y) {
+template <int F, int SRC, bool EXACT, typename TT, typename GA>
+__device__ __forceinline__ void render_issue(RenderGroup& G, const RenderArgs& a, const GA& ga, int lev0, float x, float y) {
   constexpr int NLG = 16 / F;
   const TT* tables = static_cast<const TT*>(a.tables);
-  if constexpr (!VT) {
+  if constexpr (SRC == kSrcGrid) {
+#pragma unroll
+    for (int lv = 0; lv < NLG; ++lv) {
+      const int level = lev0 + lv;                        // (< 64 / F <= GNGF_MAX_LEVELS for every form: RENDER_F)
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int f = 0; f < F; ++f) G.fv[v][lv * F + f] = 0.f;
+      G.sx[lv] = G.sy[lv] = 0.f;
+      if (EXACT || level < a.L) {
+        const int n = a.n_ls[level];
+        const Cell cell = scaled_cell(x, y, n, G.sx[lv], G.sy[lv]);
+        const float* g = ga.grid + ga.goff[level] * F;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          // clamped to the level's (n + 2)^2 vertices: a coordinate outside [0, 1]^2 reads the edge, never past the grid
+          const int gx = min(max(cell.gx + (v & 1), 0), n + 1), gy = min(max(cell.gy + (v >> 1), 0), n + 1);
+          float o[F];
+          row_load<F>(g + ((int64_t)gy * (n + 2) + gx) * F, o);
+#pragma unroll
+          for (int f = 0; f < F; ++f) G.fv[v][lv * F + f] = o[f];
+        }
+      }
+    }
+  } else if constexpr (SRC == kSrcHash) {
 #pragma unroll
     for (int lv = 0; lv < NLG; ++lv) {
       const int level = lev0 + lv;
@@ -186,9 +220,9 @@ template <bool LEAKY> __device__ __forceinline__ float render_act(float z) { ret
     else if constexpr (KIN == 32) { constexpr int kF = 1; __VA_ARGS__; } /* (F = 1 at 64 features would be 64 levels) */ \
   } while (0)
 
-template <int KIN, bool LEAKY, bool EXACT, bool VT, typename TT>
+template <int KIN, bool LEAKY, bool EXACT, int SRC, typename TT>
 __global__ void __launch_bounds__(kDecThreads, 1)
-render_kernel(const RenderArgs a) {
+render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
   constexpr int S0 = KIN / 2, NG = S0 / 16;
   const int in_dim = EXACT ? KIN : a.L * a.F;
   const int out_dim = a.out_dim;
@@ -238,9 +272,9 @@ render_kernel(const RenderArgs a) {
   float xr[S0], x, y;
   RenderGroup G;
   coord(by, bx, x, y);
-  RENDER_F(render_issue<kF, VT, EXACT, TT>(G, a, h * (S0 / kF), x, y); render_combine<kF, 0>(G, xr));
+  RENDER_F(render_issue<kF, SRC, EXACT, TT>(G, a, ga, h * (S0 / kF), x, y); render_combine<kF, 0>(G, xr));
   if constexpr (NG == 2)
-    RENDER_F(render_issue<kF, VT, EXACT, TT>(G, a, h * (S0 / kF) + 16 / kF, x, y); render_combine<kF, 16>(G, xr));
+    RENDER_F(render_issue<kF, SRC, EXACT, TT>(G, a, ga, h * (S0 / kF) + 16 / kF, x, y); render_combine<kF, 16>(G, xr));
   for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
     const int64_t pr = by * kRenderRows + lr, pc = bx * kRenderCols + lc;         // this block's pixel
     int64_t nrow = by + gq, ncol = bx + gr;
@@ -259,7 +293,7 @@ render_kernel(const RenderArgs a) {
       acc1[1] = MFMA(a0r[1][sx], xr[sx], acc1[1]);
     }
     __builtin_amdgcn_sched_barrier(0);
-    RENDER_F(render_issue<kF, VT, EXACT, TT>(G, a, h * (S0 / kF), x, y));
+    RENDER_F(render_issue<kF, SRC, EXACT, TT>(G, a, ga, h * (S0 / kF), x, y));
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -274,7 +308,7 @@ render_kernel(const RenderArgs a) {
     }
     __builtin_amdgcn_sched_barrier(0);
     RENDER_F(render_combine<kF, 0>(G, xr));
-    if constexpr (NG == 2) RENDER_F(render_issue<kF, VT, EXACT, TT>(G, a, h * (S0 / kF) + 16 / kF, x, y));
+    if constexpr (NG == 2) RENDER_F(render_issue<kF, SRC, EXACT, TT>(G, a, ga, h * (S0 / kF) + 16 / kF, x, y));
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -312,14 +346,19 @@ render_kernel(const RenderArgs a) {
 }
 #undef RENDER_F
 
-using RenderKern = void (*)(const RenderArgs);
+using RenderKern = void (*)(const RenderArgs, const RenderNoGrid);
 template <int KIN, typename TT> static RenderKern render_pick(bool leaky, bool exact, bool vt) {
   if (leaky) {
-    if (exact) return vt ? render_kernel<KIN, true, true, true, TT> : render_kernel<KIN, true, true, false, TT>;
-    return vt ? render_kernel<KIN, true, false, true, TT> : render_kernel<KIN, true, false, false, TT>;
+    if (exact) return vt ? render_kernel<KIN, true, true, kSrcTable, TT> : render_kernel<KIN, true, true, kSrcHash, TT>;
+    return vt ? render_kernel<KIN, true, false, kSrcTable, TT> : render_kernel<KIN, true, false, kSrcHash, TT>;
   }
-  if (exact) return vt ? render_kernel<KIN, false, true, true, TT> : render_kernel<KIN, false, true, false, TT>;
-  return vt ? render_kernel<KIN, false, false, true, TT> : render_kernel<KIN, false, false, false, TT>;
+  if (exact) return vt ? render_kernel<KIN, false, true, kSrcTable, TT> : render_kernel<KIN, false, true, kSrcHash, TT>;
+  return vt ? render_kernel<KIN, false, false, kSrcTable, TT> : render_kernel<KIN, false, false, kSrcHash, TT>;
+}
+using RenderGridKern = void (*)(const RenderArgs, const RenderGridArgs);
+template <int KIN> static RenderGridKern render_pick_grid(bool leaky, bool exact) {
+  if (leaky) return exact ? render_kernel<KIN, true, true, kSrcGrid, float> : render_kernel<KIN, true, false, kSrcGrid, float>;
+  return exact ? render_kernel<KIN, false, true, kSrcGrid, float> : render_kernel<KIN, false, false, kSrcGrid, float>;
 }
 
 }  // namespace gngf
@@ -355,6 +394,43 @@ extern "C" int gngf_render(const void* tables, int feat_dtype, const int32_t* ve
   RenderKern fn;
   if (in_dim <= 32) fn = f16 ? render_pick<32, __half>(leaky != 0, in_dim == 32, vt) : render_pick<32, float>(leaky != 0, in_dim == 32, vt);
   else fn = f16 ? render_pick<64, __half>(leaky != 0, in_dim == 64, vt) : render_pick<64, float>(leaky != 0, in_dim == 64, vt);
-  fn<<<dim3(grid), dim3(kDecThreads), smem, as_stream(stream)>>>(a);
+  fn<<<dim3(grid), dim3(kDecThreads), smem, as_stream(stream)>>>(a, RenderNoGrid{});
+  GNGF_RETURN_LAUNCH();
+}
+
+// gngf_render from a baked vertex grid (the grid source above).  See include/gngf.h.
+extern "C" int gngf_render_grid(const float* grid, const int32_t* n_ls, const int32_t* n_ls_host,
+                                const float* W0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
+                                float* rgb, int32_t* img, int64_t rows, int64_t cols, int64_t r0, int64_t c0, float denom,
+                                int L, int F, int out_dim, int leaky, void* stream) {
+  constexpr int64_t kExact = (int64_t)1 << 24;
+  GNGF_CHECK_ARG(L > 0 && L <= GNGF_MAX_LEVELS && (F == 1 || F == 2 || F == 4) && L * F <= 64);
+  GNGF_CHECK_ARG(out_dim > 0 && out_dim <= 4);
+  GNGF_CHECK_ARG(rows >= 1 && cols >= 1 && denom > 0.f && r0 >= -kExact && c0 >= -kExact && r0 + rows <= kExact && c0 + cols <= kExact);
+  GNGF_CHECK_ARG(grid && n_ls && n_ls_host && W0 && b0 && W1 && b1 && W2 && b2 && (rgb || img));
+  GNGF_CHECK_ARG((reinterpret_cast<uintptr_t>(grid) & 15) == 0);
+  RenderArgs a;
+  a.tables = nullptr; a.vert_idx = nullptr; a.vert_w = nullptr; a.n_ls = n_ls;
+  a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2;
+  a.rgb = rgb; a.img = img;
+  a.rows = rows; a.cols = cols; a.r0 = r0; a.c0 = c0; a.denom = denom;
+  a.L = L; a.F = F; a.T = 0; a.K = 0; a.vstride = 0; a.NV = 0;
+  a.out_dim = out_dim; a.pow2 = false;
+  RenderGridArgs ga;
+  ga.grid = grid;
+  int64_t vtot = 0;
+  for (int l = 0; l < GNGF_MAX_LEVELS; ++l) {
+    ga.goff[l] = vtot;
+    if (l < L) {
+      GNGF_CHECK_ARG(n_ls_host[l] >= 0);
+      vtot += (int64_t)(n_ls_host[l] + 2) * (n_ls_host[l] + 2);
+    }
+  }
+  const int in_dim = L * F;
+  const int64_t nblocks = ((cols + kRenderCols - 1) / kRenderCols) * ((rows + kRenderRows - 1) / kRenderRows);
+  const unsigned nwg = (unsigned)(nblocks < 256 ? nblocks : 256);       // one persistent workgroup per CU
+  const size_t smem = sizeof(float) * (size_t)raw_offsets(in_dim).total;
+  const RenderGridKern fn = in_dim <= 32 ? render_pick_grid<32>(leaky != 0, in_dim == 32) : render_pick_grid<64>(leaky != 0, in_dim == 64);
+  fn<<<dim3(nwg), dim3(kDecThreads), smem, as_stream(stream)>>>(a, ga);
   GNGF_RETURN_LAUNCH();
 }

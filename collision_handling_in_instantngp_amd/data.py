@@ -9,6 +9,7 @@ written against it finds the same names and conventions:
   save_checkpoint / load_checkpoint        functions.py:761-781, models.py HPD/encoding weight paths: the five
                                            state-dict files of the reference, loadable in either direction
   save_snapshot                            the same five files from the best state train.fit kept on the device
+  save_baked / load_baked                  a train.BakedGrid (vertex grids + decoder: the picture without the model) as one file
 
 Host-side numpy/torch only, with one exception: reassemble_image_device runs the image scatter kernel (csrc/metrics.hip,
 through ops.image_scatter) and needs device tensors."""
@@ -177,3 +178,38 @@ def load_checkpoint(net, folder: str, optimizer=None, parts=("model",), map_loca
         target.load_state_dict(state)
     if optimizer is not None:
         optimizer.load_state_dict(torch.load(os.path.join(folder, CHECKPOINT_FILES["optimizer"]), map_location=map_location))
+
+
+BAKED_FORMAT = "gngf-baked-grid/1"
+BAKED_FIELDS = ("grid", "decoder", "n_ls_host", "L", "F", "out_dim", "leaky")      # train.BakedGrid.FIELDS
+
+
+def save_baked(baked, path: str) -> None:
+    """One file for a train.BakedGrid: a dict of tensors and plain numbers — the format tag, the field list and the fields
+    (grid, the six decoder tensors, the level resolutions, L, F, out_dim, leaky), tensors moved to the host.  The model, its
+    HPD and its tables are not needed to draw the picture again (load_baked(path).render(...))."""
+    state = {"format": BAKED_FORMAT, "fields": list(BAKED_FIELDS),
+             "grid": baked.grid.detach().cpu(), "decoder": [t.detach().cpu() for t in baked.decoder],
+             "n_ls_host": [int(n) for n in baked.n_ls_host], "L": int(baked.L), "F": int(baked.F), "out_dim": int(baked.out_dim),
+             "leaky": bool(baked.leaky)}
+    torch.save(state, path)
+
+
+def load_baked(path: str, device="cuda"):
+    """The train.BakedGrid that save_baked wrote, on `device`.  ValueError for a file with another format tag or field list, or
+    whose shapes do not fit its own numbers (grid rows for the resolutions, decoder widths for L F and out_dim)."""
+    from . import train
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(state, dict) or state.get("format") != BAKED_FORMAT or tuple(state.get("fields", ())) != BAKED_FIELDS:
+        tag = state.get("format") if isinstance(state, dict) else type(state).__name__
+        raise ValueError(f"{path} is not a baked grid of format {BAKED_FORMAT!r} (found {tag!r})")
+    missing = [k for k in BAKED_FIELDS if k not in state]
+    if missing:
+        raise ValueError(f"{path} lacks the fields {missing}")
+    if not torch.is_tensor(state["grid"]) or not all(torch.is_tensor(t) for t in state["decoder"]):
+        raise ValueError(f"{path}: grid and decoder must be tensors")
+    baked = train.BakedGrid(state["grid"].to(device), [t.to(device) for t in state["decoder"]], state["n_ls_host"], state["leaky"])
+    if (baked.L, baked.F, baked.out_dim) != (state["L"], state["F"], state["out_dim"]):
+        raise ValueError(f"{path}: tensors of L, F, out_dim = {(baked.L, baked.F, baked.out_dim)} but the file says "
+                         f"{(state['L'], state['F'], state['out_dim'])}")
+    return baked

@@ -2039,6 +2039,62 @@ def render_lattice(tables, n_ls, decoder_params, rows, cols, denom, origin=(0, 0
          float(denom), L, F, T, K, MODE_VERTEX_TABLE if vt else MODE_HASH, int(vstride), NV, C, int(bool(leaky)), stream_ptr())
 
 
+def _grid_vertices(n_ls_host):
+    return sum((int(n) + 2) ** 2 for n in n_ls_host)
+
+
+def bake_vertex_grid(tables, n_ls, n_ls_host, vert_idx, vert_w, vstride, NV, F, T, K, out=None):
+    """The vertex grid of EVERY level for the current tables: G (sum_l (N_l + 2)^2, F) fp32 with
+    G[goff_l + gy (N_l + 2) + gx] = sum_k vert_w[v, k] tables[l, vert_idx[v, k]] (v = gy vstride + gx; vert_idx None: the row
+    spatial_hash(gx, gy) itself) — gngf_vertex_grid_fwd with Ls = L, the vertex stage of a training step.  tables (L,T,F)
+    fp32 | fp16, n_ls (L) int32 and its host mirror, vert_idx / vert_w (NV,K).  out: the grid to write instead of a new one.
+    No autograd, no StepConfig: this is not a step of training."""
+    L = len(n_ls_host)
+    if tuple(tables.shape) != (L, T, F) or n_ls.numel() != L:
+        raise ValueError(f"bake_vertex_grid: tables (L,T,F) = ({L}, {T}, {F}) and {L} resolutions expected, got "
+                         f"{tuple(tables.shape)} and {n_ls.numel()}")
+    vt = vert_idx is not None
+    K = check_topk(K) if vt else 0
+    if vt and (tuple(vert_idx.shape) != (NV, K) or tuple(vert_w.shape) != (NV, K)):
+        raise ValueError(f"vert_idx and vert_w must be (NV, K) = ({NV}, {K}), got {tuple(vert_idx.shape)}, {tuple(vert_w.shape)}")
+    vtot = _grid_vertices(n_ls_host)
+    if out is None:
+        out = torch.empty((vtot, F), dtype=_f32, device=tables.device)
+    elif out.numel() != vtot * F:
+        raise ValueError(f"out holds {out.numel()} elements for a grid of {vtot} x {F}")
+    call("gngf_vertex_grid_fwd", *_tab(tables), ptr(vert_idx, _i32, "vert_idx"), ptr(vert_w, _f32, "vert_w"), ptr(n_ls, _i32, "n_ls"),
+         (_ct.c_int32 * L)(*[int(n) for n in n_ls_host]), ptr(out, _f32, "out"), L, int(F), int(T), K,
+         MODE_VERTEX_TABLE if vt else MODE_HASH, int(vstride) if vt else 0, int(NV) if vt else 0, stream_ptr())
+    return out
+
+
+def render_grid(grid, n_ls, n_ls_host, decoder_params, rows, cols, denom, origin=(0, 0), *, leaky=False, out_rgb=None,
+                out_image=None):
+    """render_lattice from a baked vertex grid (bake_vertex_grid's layout; csrc/render.inc: gngf_render_grid): the four corner
+    rows of a level are dense loads from grid (vtot, F) fp32 — no tables, no vert_idx / vert_w, no hash.  Corners are clamped
+    to the level's grid, so no coordinate faults; only coordinates in [0, 1]^2 give the model's values."""
+    L = len(n_ls_host)
+    W0, b0, W1, b1, W2, b2 = decoder_params
+    C = W2.shape[0]
+    vtot = _grid_vertices(n_ls_host)
+    if grid.dim() != 2 or grid.shape[0] != vtot:
+        raise ValueError(f"render_grid: grid must be ({vtot}, F) for these resolutions, got {tuple(grid.shape)}")
+    F = int(grid.shape[1])
+    if tuple(W0.shape) != (64, L * F) or tuple(W1.shape) != (64, 64) or W2.shape[1] != 64:
+        raise ValueError(f"render_grid: decoder ({L * F} -> 64 -> 64 -> C) expected, got {tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
+    if n_ls.numel() != L:
+        raise ValueError(f"n_ls holds {n_ls.numel()} resolutions for {L} levels")
+    if out_rgb is None and out_image is None:
+        raise ValueError("render_grid: pass out_rgb, out_image or both")
+    for name, t in (("out_rgb", out_rgb), ("out_image", out_image)):
+        if t is not None and t.numel() != rows * cols * C:
+            raise ValueError(f"{name} holds {t.numel()} elements for a {rows} x {cols} x {C} render")
+    call("gngf_render_grid", ptr(grid, _f32, "grid"), ptr(n_ls, _i32, "n_ls"), (_ct.c_int32 * L)(*[int(n) for n in n_ls_host]),
+         ptr(W0, _f32, "W0"), ptr(b0, _f32, "b0"), ptr(W1, _f32, "W1"), ptr(b1, _f32, "b1"), ptr(W2, _f32, "W2"), ptr(b2, _f32, "b2"),
+         ptr(out_rgb, _f32, "out_rgb"), ptr(out_image, _i32, "out_image"), int(rows), int(cols), int(origin[0]), int(origin[1]),
+         float(denom), L, F, C, int(bool(leaky)), stream_ptr())
+
+
 # Keep the decoder's activated hidden layers (512 B / pixel) from forward to backward instead of recomputing them: the
 # stores and loads ride under the MFMAs of kernels that leave most of the HBM bandwidth unused (decoder backward 345 -> ~230 us
 # at 2^20 px).  False: recompute (no extra memory).

@@ -1303,30 +1303,58 @@ def lattice_coordinates(rows, cols, denom, origin=(0, 0)):
     return np.stack([np.repeat(rr, cols), np.tile(cc, rows)], axis=1)
 
 
+_GENERAL_PATH = " — evaluate net(x) on explicit coordinates instead"
+
+
+def _check_render_model(net, who):
+    """What the render kernel holds, for render() and bake(): the decoder's output width C, or ValueError naming net(x)."""
+    general = _GENERAL_PATH
+    if models.should_batchnorm_data:
+        raise ValueError(f"{who}: should_batchnorm_data normalises coordinates with batch statistics, a lattice has none" + general)
+    widths = [tuple(seq[0].weight.shape) for seq in net.mlp]
+    L, F = net._num_levels, net._feature_dim
+    if len(widths) != 3 or widths[0] != (64, L * F) or widths[1] != (64, 64) or widths[2][1] != 64 or widths[2][0] > 4:
+        raise ValueError(f"{who}: the render kernel holds a decoder with hidden widths [64, 64] and at most 4 outputs, this one is "
+                         f"{[w[::-1] for w in widths]}" + general)
+    if L * F > 64:
+        raise ValueError(f"{who}: L * F = {L * F} encoder features, the render kernel holds at most 64" + general)
+    if F not in (1, 2, 4):
+        raise ValueError(f"{who}: feature_dim = {F}, the render kernel gathers rows of 1, 2 or 4 features" + general)
+    return widths[2][0]
+
+
+def _check_unit_square(rows, cols, r0, c0, denom, why):
+    d = np.float32(denom)
+    hi = max(np.float32(r0 + rows - 1) / d, np.float32(c0 + cols - 1) / d)
+    if r0 < 0 or c0 < 0 or hi > 1:
+        raise ValueError(f"{why} over [0, 1]^2; this lattice spans [{r0 / float(d):g}, {float(hi):g}]" + _GENERAL_PATH)
+
+
 def _render_setup(net, rows, cols, denom, origin):
     """Validation shared by render(): (rows, cols, r0, c0, denom, C) or ValueError naming net(x) as the general path."""
     if denom is None:
         denom = max(int(rows), int(cols)) - 1           # data.normalise_coordinates: the longer side spans [0, 1]
     rows, cols, r0, c0 = _check_lattice(rows, cols, denom, origin)
-    general = " — evaluate net(x) on explicit coordinates instead"
-    if models.should_batchnorm_data:
-        raise ValueError("render(): should_batchnorm_data normalises coordinates with batch statistics, a lattice has none" + general)
-    widths = [tuple(seq[0].weight.shape) for seq in net.mlp]
-    L, F = net._num_levels, net._feature_dim
-    if len(widths) != 3 or widths[0] != (64, L * F) or widths[1] != (64, 64) or widths[2][1] != 64 or widths[2][0] > 4:
-        raise ValueError(f"render(): the render kernel holds a decoder with hidden widths [64, 64] and at most 4 outputs, this one is "
-                         f"{[w[::-1] for w in widths]}" + general)
-    if L * F > 64:
-        raise ValueError(f"render(): L * F = {L * F} encoder features, the render kernel holds at most 64" + general)
-    if F not in (1, 2, 4):
-        raise ValueError(f"render(): feature_dim = {F}, the render kernel gathers rows of 1, 2 or 4 features" + general)
+    C = _check_render_model(net, "render()")
     if not net._hash_mode:
-        d = np.float32(denom)
-        hi = max(np.float32(r0 + rows - 1) / d, np.float32(c0 + cols - 1) / d)
-        if r0 < 0 or c0 < 0 or hi > 1:
-            raise ValueError(f"render(): GNGF indexing looks vertices up in the table over [0, 1]^2; this lattice spans "
-                             f"[{r0 / float(d):g}, {float(hi):g}]" + general)
-    return rows, cols, r0, c0, float(np.float32(denom)), widths[2][0]
+        _check_unit_square(rows, cols, r0, c0, denom, "render(): GNGF indexing looks vertices up in the table")
+    return rows, cols, r0, c0, float(np.float32(denom)), C
+
+
+def _render_outputs(rows, cols, C, dev, rgb, image, out_rgb, out_image, who):
+    """The (out_rgb, out_image) a render writes — None where not asked for — new tensors on dev unless given; ValueError for a
+    buffer of the wrong kind or size."""
+    rgb, image = bool(rgb) or out_rgb is not None, bool(image) or out_image is not None
+    if not (rgb or image):
+        raise ValueError(f"{who}: ask for rgb, image or both")
+    for name, t, dt in (("out_rgb", out_rgb, torch.float32), ("out_image", out_image, torch.int32)):
+        if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() != rows * cols * C):
+            raise ValueError(f"{name} must be a contiguous device {dt} tensor of {rows} x {cols} x {C} elements")
+    if rgb and out_rgb is None:
+        out_rgb = torch.empty((rows * cols, C), dtype=torch.float32, device=dev)
+    if image and out_image is None:
+        out_image = torch.empty((rows, cols, C) if C != 1 else (rows, cols), dtype=torch.int32, device=dev)
+    return out_rgb, out_image
 
 
 @torch.no_grad()
@@ -1360,35 +1388,22 @@ def render(net, rows, cols, denom=None, origin=(0, 0), *, rgb=True, image=False,
     ValueError: should_batchnorm_data, a decoder other than [64, 64] with at most 4 outputs, L * F > 64, F not in {1, 2, 4} —
     net(x) is the general path."""
     rows, cols, r0, c0, denom, C = _render_setup(net, rows, cols, denom, origin)
-    rgb, image = bool(rgb) or out_rgb is not None, bool(image) or out_image is not None
-    if not (rgb or image):
-        raise ValueError("render(): ask for rgb, image or both")
     tables = net.encoding.packed_tables()
     dev = tables.device
-    if rgb and out_rgb is None:
-        out_rgb = torch.empty((rows * cols, C), dtype=torch.float32, device=dev)
-    if image and out_image is None:
-        out_image = torch.empty((rows, cols, C) if C != 1 else (rows, cols), dtype=torch.int32, device=dev)
-    for name, t, dt in (("out_rgb", out_rgb, torch.float32), ("out_image", out_image, torch.int32)):
-        if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() != rows * cols * C):
-            raise ValueError(f"{name} must be a contiguous device {dt} tensor of {rows} x {cols} x {C} elements")
+    out_rgb, out_image = _render_outputs(rows, cols, C, dev, rgb, image, out_rgb, out_image, "render()")
     ti = w = None
     vstride = 0
     if not net._hash_mode:
         ti, w, vstride = _render_vertex_table(net)
     ops.render_lattice(tables, net._n_ls_flat(dev), [p.detach() for p in net._decoder_params()], rows, cols, denom, (r0, c0),
-                       vert_idx=ti, vert_w=w, vstride=vstride, leaky=net._leaky, out_rgb=out_rgb if rgb else None,
-                       out_image=out_image if image else None)
-    if rgb and image:
+                       vert_idx=ti, vert_w=w, vstride=vstride, leaky=net._leaky, out_rgb=out_rgb, out_image=out_image)
+    if out_rgb is not None and out_image is not None:
         return out_rgb, out_image
-    return out_rgb if rgb else out_image
+    return out_rgb if out_rgb is not None else out_image
 
 
-def render_psnr(net, og_image):
-    """Renders the model at og_image's own lattice — (h,w,3) or (h,w), whole values 0..255, what calc_psnr would be handed — and
-    scores it: (image int32 device tensor of og_image's shape, psnr, accuracy), the numbers formed as EpochImage.psnr() /
-    .accuracy() form them (integer sums on the device — gngf_image_metrics — floats on the host).  After fit():
-    `res.best.restore(); image, psnr, acc = render_psnr(net, og_image)` is the best model's picture and score."""
+def _score_render(render_image, out_dim, og_image):
+    """render_psnr of the model and of a BakedGrid: render_image(h, w) -> int32 device image, scored against og_image."""
     og = np.asarray(og_image)
     if og.ndim not in (2, 3) or og.size == 0 or (og.ndim == 3 and not 1 <= og.shape[2] <= 4):
         raise ValueError(f"og_image must be (h,w) or (h,w,C) with C <= 4, got {og.shape}")
@@ -1397,12 +1412,120 @@ def render_psnr(net, og_image):
         raise ValueError("og_image must hold whole values in 0..255")
     h, w = int(og.shape[0]), int(og.shape[1])
     C = 1 if og.ndim == 2 else int(og.shape[2])
-    if net.mlp[-1][0].weight.shape[0] != C:
-        raise ValueError(f"og_image has {C} channel(s), the model {net.mlp[-1][0].weight.shape[0]}")
-    img = render(net, h, w, rgb=False, image=True)
+    if out_dim != C:
+        raise ValueError(f"og_image has {C} channel(s), the model {out_dim}")
+    img = render_image(h, w)
     dev = img.device
     n = h * w * C
     sums = ops.image_metrics(img, torch.from_numpy(np.ascontiguousarray(t8).reshape(-1)).to(dev),
                              torch.zeros((2,), dtype=torch.int64, device=dev), ops.image_metrics_workspace(n, dev))
     eq, sse = sums.cpu().numpy()
     return img.view(og.shape), float(psnr_from_sums(sse, n, 20 * np.log10(np.max(og_image)))), float((eq / n) * 100)
+
+
+def render_psnr(net, og_image):
+    """Renders the model at og_image's own lattice — (h,w,3) or (h,w), whole values 0..255, what calc_psnr would be handed — and
+    scores it: (image int32 device tensor of og_image's shape, psnr, accuracy), the numbers formed as EpochImage.psnr() /
+    .accuracy() form them (integer sums on the device — gngf_image_metrics — floats on the host).  After fit():
+    `res.best.restore(); image, psnr, acc = render_psnr(net, og_image)` is the best model's picture and score."""
+    return _score_render(lambda h, w: render(net, h, w, rgb=False, image=True), net.mlp[-1][0].weight.shape[0], og_image)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Baking: once training stops, sum_k w[v, k] table[l, idx[v, k]] is a constant of the (level, vertex) — the vertex grid of a
+# training step, over all L levels.  A BakedGrid holds that grid and a copy of the decoder: the picture without the model.
+
+def baked_level_offsets(n_ls_host):
+    """(offsets, vtot) of a baked grid: level l's (N_l + 2) x (N_l + 2) vertices are rows offsets[l] + gy (N_l + 2) + gx of the
+    (vtot, F) grid, offsets[l] = sum_{j<l} (N_j + 2)^2 (include/gngf.h: gngf_vertex_grid_fwd).  A coordinate in [0, 1] reaches
+    corners 0 .. floor(N_l) + 1 = N_l + 1 per axis: all inside the level."""
+    offsets, vtot = [], 0
+    for n in n_ls_host:
+        offsets.append(vtot)
+        vtot += (int(n) + 2) ** 2
+    return offsets, vtot
+
+
+class BakedGrid:
+    """A model baked for inference (bake()): `grid` (vtot, F) fp32 in baked_level_offsets' layout, `decoder` — COPIES of the
+    six decoder tensors [W0, b0, W1, b1, W2, b2] — and the level resolutions (`n_ls` int32 on the grid's device, `n_ls_host`
+    the same as a list), with L, F, out_dim, leaky and nbytes (grid + decoder).  It holds no reference to the model, its HPD
+    or its tables; data.save_baked / load_baked store and read exactly these fields.
+    A SNAPSHOT: nothing ties it to the weights it was baked from — bake again (bake(net, out=baked)) after they change."""
+
+    FIELDS = ("grid", "decoder", "n_ls_host", "L", "F", "out_dim", "leaky")
+
+    def __init__(self, grid, decoder, n_ls_host, leaky, n_ls=None):
+        n_ls_host = [int(n) for n in n_ls_host]
+        L, vtot = len(n_ls_host), baked_level_offsets(n_ls_host)[1]
+        decoder = list(decoder)
+        if grid.dim() != 2 or grid.shape[0] != vtot or grid.shape[1] not in (1, 2, 4) or grid.dtype != torch.float32:
+            raise ValueError(f"grid must be float32 ({vtot}, F) with F in (1, 2, 4) for resolutions {n_ls_host}, "
+                             f"got {grid.dtype} {tuple(grid.shape)}")
+        F = int(grid.shape[1])
+        shapes = [tuple(t.shape) for t in decoder]
+        C = shapes[4][0] if len(shapes) == 6 and len(shapes[4]) == 2 else 0
+        if not 0 < L <= 32 or L * F > 64 or not 1 <= C <= 4 or shapes != [(64, L * F), (64,), (64, 64), (64,), (C, 64), (C,)] \
+                or any(t.dtype != torch.float32 or t.device != grid.device for t in decoder):
+            raise ValueError(f"decoder must be float32 [W0 (64, {L * F}), b0, W1 (64, 64), b1, W2 (C, 64), b2] with C <= 4 on "
+                             f"{grid.device}, got {shapes}")
+        self.grid, self.decoder = grid.contiguous(), [t.contiguous() for t in decoder]
+        self.n_ls_host = n_ls_host
+        self.n_ls = n_ls if n_ls is not None else torch.tensor(n_ls_host, dtype=torch.int32, device=grid.device)
+        self.L, self.F, self.out_dim, self.leaky = L, F, C, bool(leaky)
+        self.nbytes = sum(t.numel() * t.element_size() for t in [self.grid, *self.decoder])
+
+    @torch.no_grad()
+    def render(self, rows, cols, denom=None, origin=(0, 0), *, rgb=True, image=False, out_rgb=None, out_image=None):
+        """train.render's contract, return shapes and output validation, from the baked grid: one launch of gngf_render_grid,
+        no allocation when every requested output is given.  The lattice must lie inside [0, 1]^2 whatever the model's index
+        source was — a baked hash model has no rows beyond its grids."""
+        if denom is None:
+            denom = max(int(rows), int(cols)) - 1
+        rows, cols, r0, c0 = _check_lattice(rows, cols, denom, origin)
+        _check_unit_square(rows, cols, r0, c0, denom, "BakedGrid.render(): a baked model holds the vertices of its levels")
+        out_rgb, out_image = _render_outputs(rows, cols, self.out_dim, self.grid.device, rgb, image, out_rgb, out_image,
+                                             "BakedGrid.render()")
+        ops.render_grid(self.grid, self.n_ls, self.n_ls_host, self.decoder, rows, cols, float(np.float32(denom)), (r0, c0),
+                        leaky=self.leaky, out_rgb=out_rgb, out_image=out_image)
+        if out_rgb is not None and out_image is not None:
+            return out_rgb, out_image
+        return out_rgb if out_rgb is not None else out_image
+
+    def render_psnr(self, og_image):
+        """train.render_psnr of the baked picture: (image, psnr, accuracy)."""
+        return _score_render(lambda h, w: self.render(h, w, rgb=False, image=True), self.out_dim, og_image)
+
+
+@torch.no_grad()
+def bake(net, *, out=None):
+    """The model as it is NOW, baked: BakedGrid with grid[offsets[l] + gy (N_l + 2) + gx] = sum_k w[v, k] table[l, idx[v, k]]
+    — one launch of gngf_vertex_grid_fwd over all L levels, from the vertex table of the current HPD weights
+    (_render_vertex_table: the cached table of a frozen HPD, a fresh evaluation of a trainable one) or, in hash mode, from the
+    hashed rows themselves — and copies of the decoder tensors.  out: a BakedGrid of the same shape to refresh in place (grid
+    and decoder copies; no allocation).
+    A bake is a snapshot.  FusedAdam and DeviceSnapshot.restore() write weights through raw pointers, so nothing can vouch for
+    its freshness: the caller bakes again after the weights change.
+    ValueError for what render() refuses: should_batchnorm_data, a decoder other than [64, 64] with at most 4 outputs,
+    L * F > 64, F not in {1, 2, 4} — net(x) is the general path."""
+    C = _check_render_model(net, "bake()")
+    tables = net.encoding.packed_tables()
+    dev = tables.device
+    L, T, F = tables.shape
+    dec = [p.detach() for p in net._decoder_params()]
+    n_ls_host = list(net._n_ls_host)
+    if out is None:
+        out = BakedGrid(torch.empty((baked_level_offsets(n_ls_host)[1], F), dtype=torch.float32, device=dev),
+                        [torch.empty(p.shape, dtype=torch.float32, device=dev) for p in dec], n_ls_host, net._leaky)
+    elif not isinstance(out, BakedGrid) or out.n_ls_host != n_ls_host or (out.F, out.out_dim, out.leaky) != (F, C, net._leaky) \
+            or out.grid.device != dev:
+        raise ValueError("bake(): out must be a BakedGrid of this model's shape (resolutions, F, outputs, activation) on its device")
+    ti = w = None
+    vstride = NV = K = 0
+    if not net._hash_mode:
+        ti, w, vstride = _render_vertex_table(net)
+        NV, K = int(ti.shape[0]), int(ti.shape[1])
+    ops.bake_vertex_grid(tables, out.n_ls, n_ls_host, ti, w, vstride, NV, F, T, K, out=out.grid)
+    for d, s in zip(out.decoder, dec):
+        d.copy_(s)
+    return out

@@ -520,6 +520,17 @@ int gngf_render(const void* tables, int feat_dtype, const int32_t* vert_idx, con
                 const float* W0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
                 float* rgb, int32_t* img, int64_t rows, int64_t cols, int64_t r0, int64_t c0, float denom,
                 int L, int F, int64_t T, int K, int mode, int vstride, int64_t NV, int out_dim, int leaky, void* stream);
+/* gngf_render from a BAKED model: grid (sum_l (N_l+2)^2, F) fp32, 16-byte aligned, is the vertex grid of every level as
+ * gngf_vertex_grid_fwd writes it with Ls = L — row goff_l + gy (N_l+2) + gx, goff_l = sum_{j<l} (N_j+2)^2 — for either index
+ * source and table type.  Corner v of a level reads row (clamp(gx + (v & 1), 0, N_l+1), clamp(gy + (v >> 1), 0, N_l+1)): four
+ * independent dense loads, no tables, no vert_idx / vert_w, no hash; a coordinate outside [0, 1]^2 never faults (it reads the
+ * grid's edge, which is not the model's value there).  n_ls (L) int32 on the device, n_ls_host its host mirror (the level
+ * offsets are formed from it and passed with the launch).  Coordinates, decoder, outputs and quantisation as gngf_render.
+ * Requires what gngf_render requires of L, F, out_dim, rows, cols, r0, c0, denom; else hipErrorInvalidValue. */
+int gngf_render_grid(const float* grid, const int32_t* n_ls, const int32_t* n_ls_host,
+                     const float* W0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
+                     float* rgb, int32_t* img, int64_t rows, int64_t cols, int64_t r0, int64_t c0, float denom,
+                     int L, int F, int out_dim, int leaky, void* stream);
 
 /* ---- epoch loop (functions.py:639-814: early stopping, the zero-collision stop, keeping the best model) ---------------
  * gngf_epoch_tail: one launch per epoch, one workgroup; takes the epoch's decisions on the device, advances `state` and
