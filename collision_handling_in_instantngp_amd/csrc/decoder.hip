@@ -23,7 +23,10 @@
 //   * v_mfma_f32_32x32x2_f32 issues back to back at exactly 64 cycles, dependent accumulator chains included;
 //   * a VALU instruction NEVER overlaps the wave's (or a sibling wave's) MFMAs: an MFMA followed by n VALU instructions
 //     costs 64 + ~10 + 4n cycles — v_accvgpr_read/write and address arithmetic included;
-//   * LDS, VMEM and scalar instructions placed between two MFMAs are free (up to ~15 per MFMA).
+//   * LDS, VMEM and scalar instructions placed between two MFMAs are free (up to ~15 per MFMA);
+//   * under a v_mfma_f32_32x32x16_bf16 (32 cycles) VALU instructions DO issue: about five per MFMA hide, a sixth and later ones
+//     cost their 4 cycles again (tools/micro/gen_mfma_bf16_mix.py found four for free).  The training kernel therefore gives
+//     every bf16 MFMA a slot of its own with <= 5-7 VALU instructions (SLOT_END below) instead of bursts between the runs.
 //   Hence: as few VALU instructions as possible (one-instruction ReLU, selects instead of mask multiplies, immediate
 //   LDS offsets instead of address adds, buffer loads/stores whose range check replaces the tail masks, loop-carried
 //   tiles pinned to AGPRs so hipcc does not shuttle them), gathered in a few bursts, and all LDS traffic of a phase
@@ -629,7 +632,8 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
   }
   unsigned dxmax = 0u;                                   // bits of the largest |d enc| this lane produced (hint for the encoder backward)
 #if defined(GNGF_STAMPS)
-  unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast;
+  unsigned ph[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // (32-bit sums: the kernel has no scalar registers to spare)
+  unsigned long long tlast;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast) :: "memory");
 #endif
   // first tile's layer-1 fragments; later tiles load theirs under the dW0 run of the tile before.  (64-wide input: the
@@ -697,15 +701,26 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
   //   R1  [x image, W1 frags]  | relu | R2 [h1 image, dz3 image, W1^T frags] + dh2 | relu, mask |
   //   dh1 [h2 image, dW2 operands -> 32 4x4 MFMAs; dz2 image; dW1 operands; h1 read-back] | mask, db1 |
   //   dW1 [dz1 image, dW0 operands, W0^T frags] | dW0 [next tile's W0 frags] | dX | |d enc| max, db0, next dz3 | stores
+  // TRAIN: the bf16 runs (layer 1, layer 2, dh1, d enc) carry the VALU work instead — one slot per MFMA —, and where two
+  // output tiles are driven together the second one trails: tile 0's last products come first, its activation / mask and the
+  // split the next phase starts with issue under tile 1's.  What stays between the runs: the split of x chunk 0, tile 1's
+  // activation of h2, the sigmoid and d rgb, the mask and split of dh2's first k-chunk, tile 1's mask of dh1, the split of
+  // d enc's first k-chunk (all next to fp32 runs, which hide nothing).
 #define STEP_END() __builtin_amdgcn_sched_barrier(0)
+// TRAIN: one bf16 MFMA and the few VALU instructions in its shadow.  The scheduling barrier alone does not hold an MFMA in its
+// slot (instruction selection may still reorder two independent accumulation chains around it): the empty asm statements make
+// the accumulators opaque at the slot's end, so each product is issued inside the slot it was written in.
+#define SLOT_END() __builtin_amdgcn_sched_barrier(0)
+#define SLOT_END1(x) do { asm volatile("" : "+a"(x)); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define SLOT_END2(x, y) do { asm volatile("" : "+a"(x), "+a"(y)); __builtin_amdgcn_sched_barrier(0); } while (0)
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     pin_acc();
     STAMP(0);
     float f1[2][32];
     if constexpr (TRAIN) {
       // ---- forward of the tile on the bf16 pipe (exact three-way split): h1 = act(W0 x + b0), h2 = act(W1 h1 + b1).
-      // Software pipeline: the planes of the next k-chunk are requested and the next chunk's operand is split while the six
-      // cross products of the current chunk (x 2 output tiles) issue; the h1 image rides under layer 2.
+      // Software pipeline: the planes of the next k-chunk are requested and the next chunk's operand is split while the
+      // cross products of the current chunk issue; the h1 image rides under layer 2.
       Planes pa0 = load_planes(w0f + lane), pa1 = load_planes(w0f + 3 * 64 + lane);
 #pragma unroll
       for (int t = 0; t < 2; ++t)
@@ -717,75 +732,104 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
           for (int e = 0; e < 4; ++e) { acc1[t][4 * g + e] = q0[e]; acc2[t][4 * g + e] = q1[e]; }
         }
       Planes zc = split8(xr[0], xr[1], xr[2], xr[3], xr[4], xr[5], xr[6], xr[7]);
-      // one pair of products (both output tiles) + a quarter of the next operand's split (values nv[2 q], nv[2 q + 1])
+      STAMP(8);
+      // Every bf16 MFMA is a slot of its own (SLOT_END pins it) with at most a handful of VALU instructions next to it: the
+      // split of the operand the next k-chunk needs, a twelfth at a time (split_twelfth), and the activations.  The two output
+      // tiles are SKEWED where a VALU burst would otherwise wait for both: tile 0 takes its last products first, and its
+      // activation and the split of the next phase's first operand issue in the shadow of tile 1's.  Every accumulator still
+      // receives its own products in the same order (mfma_cross 0 .. 5 per chunk, chunks in order).
       unsigned nh[4], nm[4], nl[4];
-      auto quarter = [&](int q, float a, float b) {
-        nh[q] = pack_hi16(b, a);
-        const float ra = trunc_residual(a), rb = trunc_residual(b);
-        nm[q] = pack_hi16(rb, ra);
-        nl[q] = pack_hi16(trunc_residual(rb), trunc_residual(ra));
+      float sra, srb;
+      auto next_planes = [&]() {
+        Planes p;
+        p.hi = u32x4{nh[0], nh[1], nh[2], nh[3]}; p.mid = u32x4{nm[0], nm[1], nm[2], nm[3]}; p.lo = u32x4{nl[0], nl[1], nl[2], nl[3]};
+        return p;
       };
-      auto take_next = [&]() {
-        zc.hi = u32x4{nh[0], nh[1], nh[2], nh[3]}; zc.mid = u32x4{nm[0], nm[1], nm[2], nm[3]}; zc.lo = u32x4{nl[0], nl[1], nl[2], nl[3]};
-      };
-      {   // layer 1, chunk 0 (carries: planes of chunk 1, split of x[8 .. 15])
-        const Planes na0 = load_planes(w0f + 2 * 3 * 64 + lane), na1 = load_planes(w0f + 3 * 3 * 64 + lane);
-        acc1[0] = mfma_b(pa0.hi, zc.lo, acc1[0]);  acc1[1] = mfma_b(pa1.hi, zc.lo, acc1[1]);  quarter(0, xr[8], xr[9]);   STEP_END();
-        acc1[0] = mfma_b(pa0.lo, zc.hi, acc1[0]);  acc1[1] = mfma_b(pa1.lo, zc.hi, acc1[1]);  quarter(1, xr[10], xr[11]); STEP_END();
-        acc1[0] = mfma_b(pa0.mid, zc.mid, acc1[0]); acc1[1] = mfma_b(pa1.mid, zc.mid, acc1[1]); quarter(2, xr[12], xr[13]); STEP_END();
-        acc1[0] = mfma_b(pa0.hi, zc.mid, acc1[0]); acc1[1] = mfma_b(pa1.hi, zc.mid, acc1[1]); quarter(3, xr[14], xr[15]); STEP_END();
-        acc1[0] = mfma_b(pa0.mid, zc.hi, acc1[0]); acc1[1] = mfma_b(pa1.mid, zc.hi, acc1[1]);
-        acc1[0] = mfma_b(pa0.hi, zc.hi, acc1[0]);  acc1[1] = mfma_b(pa1.hi, zc.hi, acc1[1]);  STEP_END();
-        take_next(); pa0 = na0; pa1 = na1;
+      {   // layer 1: tile 0, chunks 0 and 1 | tile 1, chunks 0 and 1 with tile 0's activation and layer 2's first split underneath
+        const Planes pb0 = load_planes(w0f + 2 * 3 * 64 + lane), pb1 = load_planes(w0f + 3 * 3 * 64 + lane);
+        static_for<6>([&](auto S) {                        // (the split of x[8 .. 15]: two twelfths per slot)
+          constexpr int s = S.value;
+          static_for<2>([&](auto J) {
+            constexpr int k = 2 * s + J.value;
+            split_twelfth<k>(xr[8 + 2 * (k / 3)], xr[9 + 2 * (k / 3)], nh, nm, nl, sra, srb);
+          });
+          mfma_cross<s>(pa0, zc, acc1[0]);
+          SLOT_END1(acc1[0]);
+        });
+        const Planes zn = next_planes();
+        static_for<6>([&](auto S) { mfma_cross<S.value>(pb0, zn, acc1[0]); SLOT_END1(acc1[0]); });
+        const Planes na0 = load_planes(w1f + lane), na1 = load_planes(w1f + 3 * 64 + lane);       // layer 2, chunk 0
+        static_for<12>([&](auto S) {
+          constexpr int s = S.value;
+          if constexpr (s < 6) mfma_cross<s>(pa1, zc, acc1[1]);
+          else mfma_cross<s - 6>(pb1, zn, acc1[1]);
+          SLOT_END1(acc1[1]);
+          // 16 activations (registers 0 .. 7 first: the split reads them) and 12 twelfths over 12 slots, 4 - 7 instructions each
+          constexpr int r_lo[12] = {0, 3, 6, 9, 10, 11, 11, 12, 12, 13, 13, 14}, r_hi[12] = {3, 6, 9, 10, 11, 11, 12, 12, 13, 13, 14, 16};
+          constexpr int k_lo[12] = {0, 0, 0, 1, 2, 3, 5, 6, 8, 9, 11, 12}, k_hi[12] = {0, 0, 1, 2, 3, 5, 6, 8, 9, 11, 12, 12};
+          static_for<r_hi[s] - r_lo[s]>([&](auto R) {
+            constexpr int r = r_lo[s] + R.value;
+            acc1[0][r] = hidden_act<LEAKY>(acc1[0][r]);
+            asm volatile("" : "+v"(acc1[0][r]));           // (stays in this slot)
+          });
+          static_for<k_hi[s] - k_lo[s]>([&](auto K) {
+            constexpr int k = k_lo[s] + K.value;
+            split_twelfth<k>(acc1[0][2 * (k / 3)], acc1[0][2 * (k / 3) + 1], nh, nm, nl, sra, srb);
+          });
+          SLOT_END();
+        });
+        zc = next_planes(); pa0 = na0; pa1 = na1;
       }
-      {   // layer 1, chunk 1 (carries: planes of layer 2's chunk 0)
-        const Planes na0 = load_planes(w1f + lane), na1 = load_planes(w1f + 3 * 64 + lane);
-        mfma_split2(pa0, pa1, zc, acc1[0], acc1[1]);
-        STEP_END();
-        pa0 = na0; pa1 = na1;
-      }
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc1[t][r] = hidden_act<LEAKY>(acc1[t][r]);      // (one instruction; its readers are VALU / LDS stores)
-      zc = split8(acc1[0][0], acc1[0][1], acc1[0][2], acc1[0][3], acc1[0][4], acc1[0][5], acc1[0][6], acc1[0][7]);
-      STEP_END();
+      STAMP(2);
+      STAMP(9);
+      // layer 2.  Chunks 0 .. 2: the two tiles alternate; a slot carries a twelfth of the next chunk's split, tile 1's activation
+      // of h1 (needed from chunk 2 on: eight registers under chunk 0, eight under chunk 1, two beside every one-instruction
+      // twelfth) and one store of the h1 image.  Chunk 3: tile 0 first, its activation under tile 1's six products.
       static_for<4>([&](auto CC) {
         constexpr int cc = CC.value, nc = cc + 1;
         Planes na0, na1;
         if constexpr (nc < 4) { na0 = load_planes(w1f + (2 * nc) * 3 * 64 + lane); na1 = load_planes(w1f + (2 * nc + 1) * 3 * 64 + lane); }
-        auto step = [&](auto PP, u32x4 a0, u32x4 a1, u32x4 b) {
-          constexpr int pp = PP.value;
-          acc2[0] = mfma_b(a0, b, acc2[0]);
-          acc2[1] = mfma_b(a1, b, acc2[1]);
-          if constexpr (nc < 4 && pp < 4) {
-            constexpr int t = nc >> 1, r0 = 8 * (nc & 1) + 2 * pp;
-            quarter(pp, acc1[t][r0], acc1[t][r0 + 1]);
+        static_for<12>([&](auto S) {
+          constexpr int s = S.value;
+          constexpr int t = nc < 4 ? (s & 1) : s / 6, pp = nc < 4 ? (s >> 1) : s % 6;
+          if constexpr (nc < 4) {
+            constexpr int tn = nc >> 1, r0 = 8 * (nc & 1) + 2 * (s / 3);
+            split_twelfth<s>(acc1[tn][r0], acc1[tn][r0 + 1], nh, nm, nl, sra, srb);
           }
-          if constexpr (pp < 4) {                           // h1 image (image B): 8 stores per chunk
+          if constexpr (t == 0) mfma_cross<pp>(pa0, zc, acc2[0]);
+          else mfma_cross<pp>(pa1, zc, acc2[1]);
+          if constexpr (s < 8) {                            // h1 image (image B): 8 stores per chunk
+            constexpr int e = 8 * cc + s, tt = e >> 4, r = e & 15;
+            lds_store<kImgB + (32 * tt + (r & 3) + 8 * (r >> 2)) * kImgStride * 4>(wTile, acc1[tt][r]);
+          }
+          if constexpr (cc < 2 && s % 3 == 0)
             static_for<2>([&](auto E) {
-              constexpr int e = 8 * cc + 2 * pp + E.value, tt = e >> 4, r = e & 15;
-              lds_store<kImgB + (32 * tt + (r & 3) + 8 * (r >> 2)) * kImgStride * 4>(wTile, acc1[tt][r]);
+              constexpr int r = 8 * cc + 2 * (s / 3) + E.value;
+              acc1[1][r] = hidden_act<LEAKY>(acc1[1][r]);
+              asm volatile("" : "+v"(acc1[1][r]));
             });
+          if constexpr (nc == 4 && s >= 6) SLOT_END1(acc2[1]);
+          else SLOT_END2(acc2[0], acc2[1]);
+          if constexpr (nc == 4 && s >= 6) {
+            constexpr int r_lo = s < 10 ? 3 * (s - 6) : 12 + 2 * (s - 10), n = s < 10 ? 3 : 2;
+            static_for<n>([&](auto R) {
+              constexpr int r = r_lo + R.value;
+              acc2[0][r] = hidden_act<LEAKY>(acc2[0][r]);
+              asm volatile("" : "+v"(acc2[0][r]));
+            });
+            SLOT_END();
           }
-          STEP_END();
-        };
-        step(std::integral_constant<int, 0>{}, pa0.hi, pa1.hi, zc.lo);
-        step(std::integral_constant<int, 1>{}, pa0.lo, pa1.lo, zc.hi);
-        step(std::integral_constant<int, 2>{}, pa0.mid, pa1.mid, zc.mid);
-        step(std::integral_constant<int, 3>{}, pa0.hi, pa1.hi, zc.mid);
-        step(std::integral_constant<int, 4>{}, pa0.mid, pa1.mid, zc.hi);
-        step(std::integral_constant<int, 5>{}, pa0.hi, pa1.hi, zc.hi);
-        if constexpr (nc < 4) { take_next(); pa0 = na0; pa1 = na1; }
+        });
+        if constexpr (nc < 4) { zc = next_planes(); pa0 = na0; pa1 = na1; }
       });
+      STAMP(10);
       f32x4 w2v[8];                                        // output-layer weights: requested before the activation burst
 #pragma unroll
       for (int g = 0; g < 8; ++g) w2v[g] = *reinterpret_cast<const f32x4*>(w2L + (g * 64 + lane) * 4);
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc2[t][r] = hidden_act<LEAKY>(acc2[t][r]);
+      for (int r = 0; r < 16; ++r) acc2[1][r] = hidden_act<LEAKY>(acc2[1][r]);      // (tile 0's went under tile 1's last products)
       STEP_END();                                          // (the 4x4 MFMAs below must not follow their operand's v_max directly)
+      STAMP(11);
       // ---- output layer on v_mfma_f32_4x4x1 (as decoder_fwd_kernel), rgb out, d rgb from it and the target
       {
         f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
@@ -877,6 +921,11 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
     fetch_y(tile + gridDim.x);
     MFMA_DRAIN(d2[0], d2[1]);
     STEP_END();
+    STAMP(12);
+    if constexpr (TRAIN) {                                 // k-chunk 0 of dh1 only: chunk c + 1 is masked under the products of chunk c
+#pragma unroll
+      for (int r = 0; r < 8; ++r) d2[0][r] = hidden_dsel<LEAKY>(acc2[0][r], d2[0][r]);
+    } else {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -884,6 +933,7 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
         if (RECOMPUTE) acc2[t][r] = hidden_act<LEAKY>(acc2[t][r]);
         d2[t][r] = hidden_dsel<LEAKY>(acc2[t][r], d2[t][r]);
       }
+    }
     pin_acc();
     STEP_END();
     STAMP(3);
@@ -934,6 +984,58 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
       };
       Planes zc = split8(d2[0][0], d2[0][1], d2[0][2], d2[0][3], d2[0][4], d2[0][5], d2[0][6], d2[0][7]);
       d1[0] = 0; d1[1] = 0;
+      STAMP(13);
+      if constexpr (TRAIN) {
+      // One slot per MFMA, as in the forward layers.  Chunks 0 .. 2: the tiles alternate, a slot carries a twelfth of the next
+      // chunk's split with the mask of its two values in front of the first twelfth (so the dz2 image stores of chunk 2 find all
+      // of d2 masked); the LDS traffic of a pair of products rides with the pair's first slot.  Chunk 3: tile 0 first, its mask
+      // (dz1, registers of tile 0) under tile 1's six products.
+      static_for<4>([&](auto CC) {
+        constexpr int cc = CC.value, nc = cc + 1;
+        unsigned nh[4], nm[4], nl[4];
+        float sra, srb;
+        static_for<12>([&](auto S) {
+          constexpr int s = S.value;
+          constexpr int t = nc < 4 ? (s & 1) : s / 6, pp = nc < 4 ? (s >> 1) : s % 6;
+          if constexpr (nc < 4) {
+            constexpr int tn = nc >> 1, r0 = 8 * (nc & 1) + 2 * (s / 3);
+            if constexpr (s % 3 == 0) {
+              d2[tn][r0] = hidden_dsel<LEAKY>(acc2[tn][r0], d2[tn][r0]);
+              d2[tn][r0 + 1] = hidden_dsel<LEAKY>(acc2[tn][r0 + 1], d2[tn][r0 + 1]);
+            }
+            split_twelfth<s>(d2[tn][r0], d2[tn][r0 + 1], nh, nm, nl, sra, srb);
+          }
+          mfma_cross<pp>(w1p[2 * cc + t], zc, d1[t]);
+          if constexpr ((s & 1) == 0) {
+            constexpr int lp = s >> 1;
+            constexpr int first = 8 * cc + (lp < 1 ? 0 : lp < 4 ? lp + 1 : lp + 2), count = (lp == 0 || lp == 3) ? 2 : 1;
+            static_for<count>([&](auto J) { lds_step(std::integral_constant<int, first + J.value>{}); });
+          }
+          if constexpr (nc == 4 && s >= 6) SLOT_END1(d1[1]);
+          else SLOT_END2(d1[0], d1[1]);
+          if constexpr (nc == 4 && s >= 6) {
+            constexpr int r_lo = s < 10 ? 3 * (s - 6) : 12 + 2 * (s - 10), n = s < 10 ? 3 : 2;
+            static_for<n>([&](auto R) {
+              constexpr int r = r_lo + R.value;
+              d1[0][r] = hidden_dsel<LEAKY>(acc1[0][r], d1[0][r]);
+            });
+            SLOT_END();
+          }
+        });
+        if constexpr (nc < 4) {
+          zc.hi = u32x4{nh[0], nh[1], nh[2], nh[3]}; zc.mid = u32x4{nm[0], nm[1], nm[2], nm[3]}; zc.lo = u32x4{nl[0], nl[1], nl[2], nl[3]};
+        }
+        if constexpr (cc == 1) {                           // dW2 (see the fp32 schedule below)
+          lds_wait();
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            dW2acc = __builtin_amdgcn_mfma_f32_4x4x1f32(av[q].x, bv[q].x, dW2acc, 0, 0, 0);
+            dW2acc = __builtin_amdgcn_mfma_f32_4x4x1f32(av[q].y, bv[q].y, dW2acc, 0, 0, 0);
+          }
+          STEP_END();
+        }
+      });
+      } else
       static_for<4>([&](auto CC) {
         constexpr int cc = CC.value, nc = cc + 1;
         unsigned nh[4], nm[4], nl[4];
@@ -976,6 +1078,7 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
           STEP_END();
         }
       });
+      STAMP(14);
     } else {
     {
       f32x2 av[16], bv[16];
@@ -1038,7 +1141,9 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) d1[t][r] = hidden_dsel<LEAKY>(RECOMPUTE ? h1v[t][r] : acc1[t][r], d1[t][r]);
+      for (int r = 0; r < 16; ++r)
+        if (!(TRAIN && t == 0))                            // (TRAIN: tile 0 was masked under tile 1's last products)
+          d1[t][r] = hidden_dsel<LEAKY>(RECOMPUTE ? h1v[t][r] : acc1[t][r], d1[t][r]);
     {   // db1[32a + i] += sum over this half's 16 pixels of dz2 (the A operands ARE dz2^T): 2 registers instead of 32
       f32x2 s0 = a0p[0], s1 = a1p[0];
 #pragma unroll
@@ -1145,6 +1250,19 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
           constexpr int t = nc >> 1, r0 = 8 * (nc & 1);
           nz = split8(d1[t][r0], d1[t][r0 + 1], d1[t][r0 + 2], d1[t][r0 + 3], d1[t][r0 + 4], d1[t][r0 + 5], d1[t][r0 + 6], d1[t][r0 + 7]);
         }
+        if constexpr (TRAIN && nc == 4) {
+          // nothing is left to split: the adds of the bias gradient db0 (as db1 above: the A operands of dW0 are dz1^T) take the
+          // gaps of the last chunk
+          f32x2 s0 = c0p[0], s1 = c1p[0];
+          static_for<6>([&](auto PP) {
+            constexpr int p = PP.value;
+            mfma_cross<p>(fa, zc, acc);
+            s0 += c0p[p + 1]; s1 += c1p[p + 1];
+            if constexpr (p == 5) { s0 += c0p[7]; s1 += c1p[7]; db0acc[0] += s0.x + s0.y; db0acc[1] += s1.x + s1.y; }
+            else asm volatile("" : "+v"(s0), "+v"(s1));
+            SLOT_END1(acc);
+          });
+        } else {
         // six cross terms, smallest first
         acc = mfma_b(fa.hi, zc.lo, acc);
         acc = mfma_b(fa.lo, zc.hi, acc);
@@ -1152,10 +1270,12 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
         acc = mfma_b(fa.hi, zc.mid, acc);
         acc = mfma_b(fa.mid, zc.hi, acc);
         acc = mfma_b(fa.hi, zc.hi, acc);
+        }
         STEP_END();
         if constexpr (nc < 4) zc = nz;
       });
       dxv[0] = acc;
+      STAMP(15);
     } else {
 #pragma unroll
     for (int tx = 0; tx < TX; ++tx) {
@@ -1181,13 +1301,13 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
         const unsigned a = __float_as_uint(dxv[tx][r]) & 0x7fffffffu;
         dxmax = a > dxmax ? a : dxmax;
       }
-    {
+    if constexpr (!TRAIN) {
       f32x2 s0 = c0p[0], s1 = c1p[0];
 #pragma unroll
       for (int q = 1; q < 8; ++q) { s0 += c0p[q]; s1 += c1p[q]; }
       db0acc[0] += s0.x + s0.y; db0acc[1] += s1.x + s1.y;
-    }
-    if constexpr (!TRAIN) make_dz3();                    // of tile t+1 (y, dy were requested half a tile ago)
+      make_dz3();                                        // of tile t+1 (y, dy were requested half a tile ago)
+    }                    // of tile t+1 (y, dy were requested half a tile ago)
     STEP_END();
     {
       const int64_t pt = bwd_tile(tile, ntiles);
@@ -1224,7 +1344,7 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
 
 #if defined(GNGF_STAMPS)
   if (blockIdx.x == 7 && threadIdx.x == 0)
-    for (int k = 0; k < 10; ++k) g_stamps[k] = ph[k];
+    for (int k = 0; k < 16; ++k) g_stamps[k] = ph[k];
   if (threadIdx.x == 0) g_blocktime[1][blockIdx.x & 255][1] = __builtin_readcyclecounter();
 #endif
   // non-negative floats (and NaN > inf) order like their bit patterns

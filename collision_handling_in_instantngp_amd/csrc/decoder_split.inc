@@ -54,6 +54,30 @@ __device__ __forceinline__ void mfma_split2(const Planes& a0, const Planes& a1, 
   c0 = mfma_b(a0.hi, b.hi, c0);  c1 = mfma_b(a1.hi, b.hi, c1);
 }
 
+// The same six cross terms one at a time (P = 0 .. 5, in mfma_split2's order), for the schedules that put a few VALU instructions
+// behind every single MFMA (decoder.hip, "issue model": at most five hide under one bf16 MFMA) instead of a burst behind a pair.
+template <int P> __device__ __forceinline__ void mfma_cross(const Planes& a, const Planes& b, f32x16& c) {
+  static_assert(P >= 0 && P < 6, "six cross terms");
+  if constexpr (P == 0) c = mfma_b(a.hi, b.lo, c);
+  else if constexpr (P == 1) c = mfma_b(a.lo, b.hi, c);
+  else if constexpr (P == 2) c = mfma_b(a.mid, b.mid, c);
+  else if constexpr (P == 3) c = mfma_b(a.hi, b.mid, c);
+  else if constexpr (P == 4) c = mfma_b(a.mid, b.hi, c);
+  else c = mfma_b(a.hi, b.hi, c);
+}
+// One twelfth of split8: pair q = K / 3 of the eight values (a, b = values 2 q, 2 q + 1), phase K % 3 — the packed upper halves |
+// the two first residuals and their upper halves | the two second residuals' upper halves: 1 + 5 + 5 VALU instructions, the same
+// expressions as split8.  ra / rb carry the first residuals from phase 1 to phase 2.  The empty asm statement keeps a twelfth where
+// it was written (a pure instruction may otherwise drift to its first use, past the scheduling barriers of the slots).
+template <int K> __device__ __forceinline__ void split_twelfth(float a, float b, unsigned (&hi)[4], unsigned (&mid)[4], unsigned (&lo)[4],
+                                                              float& ra, float& rb) {
+  constexpr int q = K / 3, p = K % 3;
+  static_assert(K >= 0 && K < 12, "twelve sub-steps");
+  if constexpr (p == 0) { hi[q] = pack_hi16(b, a); asm volatile("" : "+v"(hi[q])); }
+  else if constexpr (p == 1) { ra = trunc_residual(a); rb = trunc_residual(b); mid[q] = pack_hi16(rb, ra); asm volatile("" : "+v"(mid[q])); }
+  else { lo[q] = pack_hi16(trunc_residual(rb), trunc_residual(ra)); asm volatile("" : "+v"(lo[q])); }
+}
+
 // k index of a 64-wide activation at chunk cc (= 2 t + c), lane half h, element j
 __device__ __forceinline__ int kmapS(int cc, int h, int j) { return 32 * (cc >> 1) + crow(8 * (cc & 1) + j, h); }
 

@@ -17,7 +17,7 @@ slabs = torch.empty((query("gngf_decoder_bwd_slabs", P) * query("gngf_decoder_sl
 hidden = torch.empty((query("gngf_decoder_hidden_floats", P),), device=dev)
 rgb = torch.empty((P, out_dim), device=dev); denc = torch.empty_like(enc)
 def two():
-    call("gngf_decoder_fwd", ptr(enc), *[ptr(w) for w in Ws], ptr(rgb), ptr(hidden), ptr(None), 0, P, in_dim, out_dim, 0, stream_ptr())
+    call("gngf_decoder_fwd", ptr(enc), *[ptr(w) for w in Ws], ptr(rgb), ptr(hidden), P, in_dim, out_dim, 0, stream_ptr())
     call("gngf_decoder_bwd", ptr(enc), ptr(rgb), ptr(None), ptr(target), ptr(one), ptr(Ws[0]), ptr(Ws[1]), ptr(Ws[2]), ptr(Ws[3]), ptr(Ws[4]), ptr(denc), *[ptr(None)] * 6, ptr(slabs), ptr(None), ptr(hidden), ptr(None), 0, P, in_dim, out_dim, 0, stream_ptr())
 def fused():
     call("gngf_decoder_train", ptr(enc), ptr(target), ptr(one), *[ptr(w) for w in Ws], ptr(rgb), ptr(denc), *[ptr(None)] * 6, ptr(slabs), ptr(None), ptr(None), 0, P, in_dim, out_dim, 0, stream_ptr())
@@ -39,8 +39,13 @@ if os.environ.get("GNGF_LIB_PATH", "").endswith("stamps.so"):
     buf = (ctypes.c_uint64 * 16)()
     _lib.load().gngf_debug_read_stamps.argtypes = [ctypes.c_void_p]
     _lib.load().gngf_debug_read_stamps(buf)
-    names = ["load/copy", "forward (rest: act2, L3, sigmoid, d rgb)", "(dbg) fwd: bias, x split, L1, act1", "dh2+dact", "img+dW1", "dh1+dact", "img+dW0", "dX+store", "(dbg) fwd: split of chunk 0", "(dbg) fwd: L2 + h1 image"]
-    tot = sum(buf[:10])
-    for n, v in zip(names, buf[:10]):
-        print(f"  {n:28s} {v/32:9.0f} cycles/tile  {100*v/max(tot,1):5.1f}%")
+    # by stamp index (csrc/decoder.hip, STAMP(k)); printed in the order the phases run.  Every VALU burst between two matrix runs
+    # has a number of its own.
+    names = {0: "loop edge, pins", 8: "fwd: biases, split of x chunk 0", 2: "fwd: L1 run", 9: "fwd: act1 + split of L2 chunk 0",
+             10: "fwd: L2 run + h1 image", 11: "fwd: act2", 1: "fwd: L3, sigmoid, rgb, d rgb", 12: "dh2 run + drain",
+             3: "dh2 mask", 13: "dh1: split of chunk 0", 14: "dh1 run (+ dW2)", 5: "dh1 mask, db1", 4: "img+dW1", 6: "img+dW0",
+             15: "d enc: split of chunk 0 + run", 7: "|d enc| max, db0, stores"}
+    tot = sum(buf[:16])
+    for k, n in names.items():
+        print(f"  {k:2d} {n:32s} {buf[k]/32:9.0f} cycles/tile  {100*buf[k]/max(tot,1):5.1f}%")
     print("  total per tile", tot / 32)
