@@ -180,7 +180,9 @@ typedef struct gngf_bin_job {
 int gngf_bin_pixels2(const gngf_bin_job* job, float* zero_fill, int64_t zero_floats, void* stream);
 /* pixel stage forward with the vertex stage forward fused into its staging loop (bit-identical to gngf_vertex_grid_fwd +
  * gngf_encode_tiled_fwd).  Level-interleaved kernel (F = 2, fp32 tables — see gngf_tiled_interleaved_applies): both index sources;
- * generic kernel (any other shape; round 5): spatial-hash source, fp32 or fp16 tables, next_count must be NULL.
+ * generic kernel (any other shape; round 5): spatial-hash source, fp32 or fp16 tables, next_count must be NULL.  fp16 tables at a
+ * shape the level-interleaved kernel takes (F = 2 and the image fits) are rejected (hipErrorInvalidValue): the caller runs
+ * gngf_vertex_grid_fwd + gngf_encode_tiled_fwd.
  * next_count (optional): the count half of another batch's binning runs in extra workgroups at the end of the launch's grid; its
  * scatter half rides on gngf_encode_tiled_bwd(..., next_bin) of the same step. */
 int gngf_encode_tiled_fwd_fused(const float* sorted, const int32_t* items, const int32_t* n_items, int max_items,
@@ -224,8 +226,10 @@ int gngf_encode_tiled_bwd(const float* sorted, const int32_t* items, const int32
  * this launch writes (the vertex-grid gradient and the ridden decoder gradients) is NaN — checked on the device, no sync.
  * hash_dtables (optional; (L, hash_T, F) fp32 gradient buffer): spatial-hash index source on a single rank — the gather pass
  * adds every vertex's gradient straight to row _fast_hash(gx, gy) of the level's table gradient (= gngf_vertex_grid_bwd in hash
- * mode for levels [0, Ls)) and leaves dG unwritten: one launch and one round trip of dG less.  With dG = dG64 = NULL the work
- * items add their sums to those rows themselves (no vertex grid, no gather pass).
+ * mode for levels [0, Ls)) and leaves dG unwritten: one launch and one round trip of dG less.  dG is still READ there and must be
+ * zero on entry like any dG handed to this call: a work item adds what falls outside its tile's sub-grids to dG itself, and the
+ * gather pass adds dG's value to what it scatters (a dG that is not zero-filled ends up in the table rows).  With dG = dG64 = NULL
+ * the work items add their sums to those rows themselves (no vertex grid, no gather pass).
  * dG64 (optional; (vtot * F + 2) 64-bit words, ZERO on entry — gngf_encode_tiled_prepare clears it with dG_zero_words = 2) with
  * log2_pixels >= ceil(log2(P)) and a bound on |genc| (genc_absmax): the work items add their exact 64-bit fixed-point sums
  * straight into this vertex grid with global integer atomics (no partial images, no gather pass; bitwise reproducible), and
@@ -421,7 +425,8 @@ int gngf_expand_vertex_table(const float* xy, const int32_t* n_ls, const int32_t
 /* ---- pixel loss (row f1 of the scope table: the caller of the path) -------------------------------------------------
  * torch.nn.MSELoss() of utils.py:99 on the (P,out_dim) outputs: loss[0] = mean((pred - label)^2) over n elements.
  * workspace: gngf_mse_workspace_floats() floats, 8-byte aligned, zero-filled once before the first call (the kernel
- * resets it).  One launch; workgroup partials meet in a double-precision atomic. */
+ * resets it).  One launch; workgroup partials meet in a double-precision atomic.
+ * pred and label (and dpred of gngf_mse_bwd) are 16-byte aligned; anything else is rejected (hipErrorInvalidValue). */
 int gngf_mse_workspace_floats(void);
 int gngf_mse_blocks(int64_t n);      /* workgroups gngf_mse_fwd launches for n elements */
 int gngf_mse_fwd(const float* pred, const float* label, float* loss, float* workspace, int64_t n, void* stream);
