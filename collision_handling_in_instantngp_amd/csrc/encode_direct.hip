@@ -284,7 +284,8 @@ bilinear_bwd_kernel(const float2* __restrict__ xy, const int32_t* __restrict__ n
 // ------------------------------------------------------------------------------------------------
 // Fused direct encoder: coords -> (P, L*F).  One lane per (pixel, level): the L lanes of a pixel write one
 // contiguous L*F*4-byte row (128 B at L=16, F=2).
-template <int F, bool VT, typename TT>
+// ROWS (hash-family sources, VT = false): the row of a vertex — HashRows, or DenseHashRows for GNGF_MODE_DENSE_HASH (gngf_common.h).
+template <int F, bool VT, typename TT, typename ROWS = HashRows>
 __global__ void __launch_bounds__(kBlock)
 encode_fwd_kernel(const float2* __restrict__ xy, const TT* __restrict__ tables,
                   const int32_t* __restrict__ vert_idx, const float* __restrict__ vert_w,
@@ -301,14 +302,15 @@ encode_fwd_kernel(const float2* __restrict__ xy, const TT* __restrict__ tables,
   float2 c;
   if (order) { const float4 s = order[p]; c = make_float2(s.x, s.y); p = (int64_t)__float_as_int(s.z); }
   else c = xy[p];
-  const Cell cell = make_cell(c.x, c.y, n_ls[l]);
+  const int n = n_ls[l];
+  const Cell cell = make_cell(c.x, c.y, n);
   const TT* tab = tables + (int64_t)l * T * F;
   float feat[4][F];
 #pragma unroll
   for (int v = 0; v < 4; ++v) {
     const int gx = cell.gx + (v & 1), gy = cell.gy + (v >> 1);
     if constexpr (!VT) {
-      const TT* r = tab + spatial_hash(gx, gy, T, pow2) * F;
+      const TT* r = tab + ROWS::row(gx, gy, n + 2, T, pow2) * F;
 #pragma unroll
       for (int f = 0; f < F; ++f) feat[v][f] = tload(r + f);
     } else {
@@ -332,7 +334,7 @@ encode_fwd_kernel(const float2* __restrict__ xy, const TT* __restrict__ tables,
 // Backward, direct form.  One lane per (pixel, level, FEATURE), feature fastest: the F lanes of a corner add to F
 // consecutive floats of one table row, so one wave-instruction's atomics fall into 64/F rows instead of 64 — the
 // memory-side atomic unit works in 64-byte requests and merges the lanes of a row (F = 4: 4x fewer requests).
-template <int F, bool VT, typename TT>
+template <int F, bool VT, typename TT, typename ROWS = HashRows>
 __global__ void __launch_bounds__(kBlock)
 encode_bwd_kernel(const float2* __restrict__ xy, const TT* __restrict__ tables,
                   const int32_t* __restrict__ vert_idx, const float* __restrict__ vert_w,
@@ -346,7 +348,8 @@ encode_bwd_kernel(const float2* __restrict__ xy, const TT* __restrict__ tables,
   const int64_t p = pl / nl;
   const int l = l0 + (int)(pl - p * nl);
   const float2 c = xy[p];
-  const Cell cell = make_cell(c.x, c.y, n_ls[l]);
+  const int n = n_ls[l];
+  const Cell cell = make_cell(c.x, c.y, n);
   const TT* tab = tables + (int64_t)l * T * F;
   float* dtab = dtables + (int64_t)l * T * F;
   const float g = genc[(p * L + l) * F + f];
@@ -355,7 +358,7 @@ encode_bwd_kernel(const float2* __restrict__ xy, const TT* __restrict__ tables,
     const int gx = cell.gx + (v & 1), gy = cell.gy + (v >> 1);
     const float cv = cell.c[v];
     if constexpr (!VT) {
-      atomicAdd(dtab + spatial_hash(gx, gy, T, pow2) * F + f, g * cv);
+      atomicAdd(dtab + ROWS::row(gx, gy, n + 2, T, pow2) * F + f, g * cv);
     } else {
       int64_t vid = (int64_t)gy * vstride + gx;
       vid = vid < 0 ? 0 : (vid >= NV ? NV - 1 : vid);
@@ -470,7 +473,7 @@ extern "C" int gngf_encode_fwd(const float* xy, const void* tables_v, int feat_d
                                const int32_t* n_ls, float* enc, int64_t P, int L, int F, int64_t T, int K,
                                int mode, int vstride, int64_t NV, int l0, int l1, const float* pixel_order, void* stream) {
   GNGF_CHECK_ARG(P >= 0 && L > 0 && L <= GNGF_MAX_LEVELS && T > 0 && l0 >= 0 && l0 <= l1 && l1 <= L);
-  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || mode == GNGF_MODE_VERTEX_TABLE);
+  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || mode == GNGF_MODE_VERTEX_TABLE || mode == GNGF_MODE_DENSE_HASH);
   if (P == 0 || l0 == l1) return 0;
   GNGF_CHECK_ARG(xy && tables_v && n_ls && enc && (reinterpret_cast<uintptr_t>(pixel_order) & 15) == 0);
   const float4* order = reinterpret_cast<const float4*>(pixel_order);
@@ -480,6 +483,10 @@ extern "C" int gngf_encode_fwd(const float* xy, const void* tables_v, int feat_d
   const bool pow2 = (T & (T - 1)) == 0;
   if (mode == GNGF_MODE_HASH) {
     DISPATCH_TT(feat_dtype, DISPATCH_F(F, (encode_fwd_kernel<kF, false, TT><<<grid, block, 0, as_stream(stream)>>>(
+                      reinterpret_cast<const float2*>(xy), static_cast<const TT*>(tables_v), nullptr, nullptr, n_ls, enc, total, L, l0,
+                      nl, T, 0, 0, 0, pow2, order))));
+  } else if (mode == GNGF_MODE_DENSE_HASH) {
+    DISPATCH_TT(feat_dtype, DISPATCH_F(F, (encode_fwd_kernel<kF, false, TT, DenseHashRows><<<grid, block, 0, as_stream(stream)>>>(
                       reinterpret_cast<const float2*>(xy), static_cast<const TT*>(tables_v), nullptr, nullptr, n_ls, enc, total, L, l0,
                       nl, T, 0, 0, 0, pow2, order))));
   } else {
@@ -496,7 +503,7 @@ extern "C" int gngf_encode_bwd(const float* xy, const void* tables_v, int feat_d
                                int64_t P, int L, int F, int64_t T, int K, int mode, int vstride, int64_t NV,
                                int l0, int l1, void* stream) {
   GNGF_CHECK_ARG(P >= 0 && L > 0 && L <= GNGF_MAX_LEVELS && T > 0 && l0 >= 0 && l0 <= l1 && l1 <= L);
-  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || mode == GNGF_MODE_VERTEX_TABLE);
+  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || mode == GNGF_MODE_VERTEX_TABLE || mode == GNGF_MODE_DENSE_HASH);
   if (P == 0 || l0 == l1) return 0;
   GNGF_CHECK_ARG(xy && tables_v && n_ls && genc && dtables);
   const int nl = l1 - l0;
@@ -505,6 +512,10 @@ extern "C" int gngf_encode_bwd(const float* xy, const void* tables_v, int feat_d
   const bool pow2 = (T & (T - 1)) == 0;
   if (mode == GNGF_MODE_HASH) {
     DISPATCH_TT(feat_dtype, DISPATCH_F(F, (encode_bwd_kernel<kF, false, TT><<<grid, block, 0, as_stream(stream)>>>(
+                      reinterpret_cast<const float2*>(xy), static_cast<const TT*>(tables_v), nullptr, nullptr, n_ls, genc, dtables,
+                      nullptr, total, L, l0, nl, T, 0, 0, 0, pow2))));
+  } else if (mode == GNGF_MODE_DENSE_HASH) {
+    DISPATCH_TT(feat_dtype, DISPATCH_F(F, (encode_bwd_kernel<kF, false, TT, DenseHashRows><<<grid, block, 0, as_stream(stream)>>>(
                       reinterpret_cast<const float2*>(xy), static_cast<const TT*>(tables_v), nullptr, nullptr, n_ls, genc, dtables,
                       nullptr, total, L, l0, nl, T, 0, 0, 0, pow2))));
   } else {

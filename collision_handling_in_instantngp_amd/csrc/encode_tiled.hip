@@ -359,7 +359,8 @@ __device__ __forceinline__ int64_t level_offset(const int32_t* n_ls, int l) {
 }
 
 // one (level, vertex): i = gy * (N_l + 2) + gx inside level l, goff = the level's offset in G (vertices)
-template <int F, bool VT, typename TT>
+// ROWS (VT = false): the row of a vertex — HashRows, or DenseHashRows for GNGF_MODE_DENSE_HASH (gngf_common.h)
+template <int F, bool VT, typename TT, typename ROWS = HashRows>
 __device__ __forceinline__ void vertex_fwd_lane(const TT* __restrict__ tables, const int32_t* __restrict__ vert_idx,
                                                 const float* __restrict__ vert_w, float* __restrict__ G, float* __restrict__ dG_zero,
                                                 int64_t T, int K, int vstride, int64_t NV, bool pow2, int l, int gw, int i, int64_t goff,
@@ -370,7 +371,7 @@ __device__ __forceinline__ void vertex_fwd_lane(const TT* __restrict__ tables, c
 #pragma unroll
   for (int f = 0; f < F; ++f) acc[f] = 0.f;
   if constexpr (!VT) {
-    const int64_t row = spatial_hash(gx, gy, T, pow2);
+    const int64_t row = ROWS::row(gx, gy, gw, T, pow2);
     if (G) {                                      // (G == nullptr: the pixel stage gathers from the tables itself — this lane only clears)
       const TT* r = tab + row * F;
 #pragma unroll
@@ -416,7 +417,7 @@ vertex_fwd_kernel(const TT* __restrict__ tables, const int32_t* __restrict__ ver
 }
 
 // rider block `vb` of the vertex stage forward: one (level, vertex) per thread, flat over the level grids
-template <int F, bool VT, typename TT>
+template <int F, bool VT, typename TT, typename ROWS = HashRows>
 __device__ __forceinline__ void vertex_ride_block(int vb, const TT* __restrict__ tables, const int32_t* __restrict__ vert_idx,
                                                   const float* __restrict__ vert_w, const int32_t* __restrict__ n_ls, float* __restrict__ G,
                                                   float* __restrict__ dG_zero, int Ls, int64_t T, int K, int vstride, int64_t NV, bool pow2,
@@ -430,7 +431,7 @@ __device__ __forceinline__ void vertex_ride_block(int vb, const TT* __restrict__
   int l = 0, gw = n_ls[0] + 2;
   int64_t goff = 0;
   while (l + 1 < Ls && e >= goff + (int64_t)gw * gw) { goff += (int64_t)gw * gw; ++l; gw = n_ls[l] + 2; }
-  vertex_fwd_lane<F, VT, TT>(tables, vert_idx, vert_w, G, dG_zero, T, K, vstride, NV, pow2, l, gw, (int)(e - goff), goff, zero_words,
+  vertex_fwd_lane<F, VT, TT, ROWS>(tables, vert_idx, vert_w, G, dG_zero, T, K, vstride, NV, pow2, l, gw, (int)(e - goff), goff, zero_words,
                              clear_rows);
 }
 
@@ -440,7 +441,7 @@ __device__ __forceinline__ void vertex_ride_block(int vb, const TT* __restrict__
 // cross-queue dependency costs ~10 us (+ ~12 us between replays); one linear chain with riders has no such gaps.
 // (The riders sit on the SCATTER launch, 13 us alone, and the gradient clear on the count launch, 8 us alone: the other way
 // round the scatter launch took 21 us.)
-template <int F, bool VT, typename TT>
+template <int F, bool VT, typename TT, typename ROWS = HashRows>
 __global__ void __launch_bounds__(kBinThreads)
 bin_scatter_ride_kernel(const BinJobDev j, const TT* __restrict__ tables, const int32_t* __restrict__ vert_idx,
                         const float* __restrict__ vert_w, const int32_t* __restrict__ n_ls, float* __restrict__ G,
@@ -451,14 +452,14 @@ bin_scatter_ride_kernel(const BinJobDev j, const TT* __restrict__ tables, const 
     bin_scatter_block((int)blockIdx.x, j, cursor);
     return;
   }
-  vertex_ride_block<F, VT, TT>((int)blockIdx.x - j.NB, tables, vert_idx, vert_w, n_ls, G, dG_zero, Ls, T, K, vstride, NV, pow2, vtot, zero_words,
+  vertex_ride_block<F, VT, TT, ROWS>((int)blockIdx.x - j.NB, tables, vert_idx, vert_w, n_ls, G, dG_zero, Ls, T, K, vstride, NV, pow2, vtot, zero_words,
                                clear_rows);
 }
 
 // K1 with the vertex stage forward riding on it (the count keeps half of the CUs busy for ~8 us): used when the launch does
 // not carry the 64 MiB gradient clear (the fused training decoder clears that buffer between its MFMAs) — the scatter launch
 // then runs alone.
-template <int F, bool VT, typename TT>
+template <int F, bool VT, typename TT, typename ROWS = HashRows>
 __global__ void __launch_bounds__(kBinThreads)
 bin_count_vride_kernel(const BinJobDev j, const TT* __restrict__ tables, const int32_t* __restrict__ vert_idx,
                        const float* __restrict__ vert_w, const int32_t* __restrict__ n_ls, float* __restrict__ G,
@@ -469,8 +470,17 @@ bin_count_vride_kernel(const BinJobDev j, const TT* __restrict__ tables, const i
     bin_count_block((int)blockIdx.x, j, hist);
     return;
   }
-  vertex_ride_block<F, VT, TT>((int)blockIdx.x - j.NB, tables, vert_idx, vert_w, n_ls, G, dG_zero, Ls, T, K, vstride, NV, pow2, vtot, zero_words,
+  vertex_ride_block<F, VT, TT, ROWS>((int)blockIdx.x - j.NB, tables, vert_idx, vert_w, n_ls, G, dG_zero, Ls, T, K, vstride, NV, pow2, vtot, zero_words,
                                clear_rows);
+}
+
+// one vertex of a HASHED level, backward: its grid gradient g goes to row hash(gx, gy) of the level's table gradient (shared by
+// vertex_bwd_kernel and the hashed levels of vertex_dense_hash_kernel: the same operations, the same bits)
+template <int F>
+__device__ __forceinline__ void vertex_bwd_hash_add(const float (&g)[F], float* __restrict__ dtab, int gx, int gy, int64_t T, bool pow2) {
+  float* r = dtab + spatial_hash(gx, gy, T, pow2) * F;
+#pragma unroll
+  for (int f = 0; f < F; ++f) atomicAdd(r + f, g[f]);
 }
 
 template <int F, bool VT, typename TT>
@@ -495,9 +505,7 @@ vertex_bwd_kernel(const TT* __restrict__ tables, const int32_t* __restrict__ ver
   const TT* tab = tables + (int64_t)l * T * F;
   float* dtab = dtables + (int64_t)l * T * F;
   if constexpr (!VT) {
-    float* r = dtab + spatial_hash(gx, gy, T, pow2) * F;
-#pragma unroll
-    for (int f = 0; f < F; ++f) atomicAdd(r + f, g[f]);
+    vertex_bwd_hash_add<F>(g, dtab, gx, gy, T, pow2);
   } else {
     const int64_t vid = (int64_t)gy * vstride + gx;
     if (gx >= vstride || vid >= NV) return;
@@ -511,6 +519,69 @@ vertex_bwd_kernel(const TT* __restrict__ tables, const int32_t* __restrict__ ver
         atomicAdd(dtab + row * F + f, g[f] * w);
       }
       if (dvert_w) atomicAdd(dvert_w + vid * K + k, dot);
+    }
+  }
+}
+
+// GNGF_MODE_DENSE_HASH, the vertex stage as a launch of its own (gngf_vertex_grid_fwd / gngf_vertex_grid_bwd): grid = (blocks, Ls),
+// blockIdx.y = level, grid-stride inside a level.  A dense level's vertex grid IS the first gw^2 rows of its table, in the same
+// layout: the forward copies and the backward adds gw^2 F consecutive values, four per lane and trip — one 16-byte access of fp32
+// (8 bytes of fp16 storage) on either side where both of the level's bases are aligned, single values at an unaligned base (T or
+// the level offset odd, F < 4) and in the last trip.  Every value has one lane and the launches of a stream are ordered: the add is
+// a plain read-modify-write, and rows >= gw^2 of a dense level are never touched.  A hashed level runs what GNGF_MODE_HASH runs
+// per vertex (vertex_fwd_lane / vertex_bwd_hash_add): the same operations, the same bits.
+__device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 load4(const __half* p) {
+  const uint2 q = *reinterpret_cast<const uint2*>(p);
+  const __half2 a = *reinterpret_cast<const __half2*>(&q.x), b = *reinterpret_cast<const __half2*>(&q.y);
+  return make_float4(__low2float(a), __high2float(a), __low2float(b), __high2float(b));
+}
+
+template <int F, typename TT, bool BWD>
+__global__ void __launch_bounds__(256)
+vertex_dense_hash_kernel(const TT* __restrict__ tables, const int32_t* __restrict__ n_ls, float* __restrict__ G,
+                         const float* __restrict__ dG, float* __restrict__ dtables, int64_t T, bool pow2) {
+  const int l = blockIdx.y;
+  const int gw = n_ls[l] + 2;
+  const int64_t goff = level_offset(n_ls, l);
+  const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  if (DenseHashRows::dense(gw, T)) {
+    const int64_t nval = (int64_t)gw * gw * F;
+    if constexpr (!BWD) {
+      const TT* src = tables + (int64_t)l * T * F;
+      float* dst = G + goff * F;
+      const bool vec = (reinterpret_cast<uintptr_t>(src) & (4 * sizeof(TT) - 1)) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+      for (int64_t j = first * 4; j < nval; j += stride * 4) {
+        if (vec && j + 4 <= nval) *reinterpret_cast<float4*>(dst + j) = load4(src + j);
+        else for (int64_t q = j; q < j + 4 && q < nval; ++q) dst[q] = tload(src + q);
+      }
+    } else {
+      const float* src = dG + goff * F;
+      float* dst = dtables + (int64_t)l * T * F;
+      const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+      for (int64_t j = first * 4; j < nval; j += stride * 4) {
+        if (vec && j + 4 <= nval) {
+          const float4 a = load4(src + j), b = load4(dst + j);
+          *reinterpret_cast<float4*>(dst + j) = make_float4(b.x + a.x, b.y + a.y, b.z + a.z, b.w + a.w);
+        } else {
+          for (int64_t q = j; q < j + 4 && q < nval; ++q) dst[q] += src[q];
+        }
+      }
+    }
+    return;
+  }
+  for (int64_t i = first; i < (int64_t)gw * gw; i += stride) {
+    if constexpr (!BWD) {
+      vertex_fwd_lane<F, false, TT>(tables, nullptr, nullptr, G, nullptr, T, 0, 0, 0, pow2, l, gw, (int)i, goff);
+    } else {
+      const float* gp = dG + (goff + i) * F;
+      float g[F];
+      bool any = false;
+#pragma unroll
+      for (int f = 0; f < F; ++f) { g[f] = gp[f]; any |= (g[f] != 0.f); }
+      if (!any) continue;                           // vertices no pixel touched
+      const int gy = (int)i / gw, gx = (int)i - gy * gw;
+      vertex_bwd_hash_add<F>(g, dtables + (int64_t)l * T * F, gx, gy, T, pow2);
     }
   }
 }
@@ -2090,7 +2161,8 @@ extern "C" int gngf_encode_tiled_prepare(const float* xy, int64_t P, int tile_sh
   // G == NULL (spatial-hash source only): no vertex grid is wanted — the pixel stage gathers from the level tables itself
   // (gngf_encode_tiled_fwd_fused) — and the riders only clear (dG_zero / clear_rows), or do not run at all
   GNGF_CHECK_ARG(Ls > 0 && Ls <= GNGF_MAX_LEVELS && T > 0 && tables && n_ls && n_ls_host && (G || mode == GNGF_MODE_HASH));
-  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0));
+  const bool dense_hash = mode == GNGF_MODE_DENSE_HASH;   // (its riders build G with the dense rule; vert_idx / vert_w / K ignored)
+  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || dense_hash || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0));
   GNGF_CHECK_ARG(zero_fill_ok(zero_fill, zero_floats));
   const int64_t nvec = zero_fill ? zero_floats / 4 : 0;
   const int zblocks = zero_fill_blocks(nvec);
@@ -2112,6 +2184,8 @@ extern "C" int gngf_encode_tiled_prepare(const float* xy, int64_t P, int tile_sh
     // no gradient clear on this launch: the vertex riders move to the COUNT launch and the scatter launch runs alone
     if (hash) {
       DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_count_vride_kernel<kF, false, TT><<<ride_grid, block, smem, s>>>(j, VERTEX_RIDE_ARGS))));
+    } else if (dense_hash) {
+      DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_count_vride_kernel<kF, false, TT, DenseHashRows><<<ride_grid, block, smem, s>>>(j, VERTEX_RIDE_ARGS))));
     } else {
       DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_count_vride_kernel<kF, true, TT><<<ride_grid, block, smem, s>>>(j, VERTEX_RIDE_ARGS))));
     }
@@ -2127,6 +2201,8 @@ extern "C" int gngf_encode_tiled_prepare(const float* xy, int64_t P, int tile_sh
   launch_bin_scans(j, s);
   if (hash) {
     DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_scatter_ride_kernel<kF, false, TT><<<ride_grid, block, smem, s>>>(j, VERTEX_RIDE_ARGS))));
+  } else if (dense_hash) {
+    DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_scatter_ride_kernel<kF, false, TT, DenseHashRows><<<ride_grid, block, smem, s>>>(j, VERTEX_RIDE_ARGS))));
   } else {
     DISPATCH_TT(feat_dtype, DISPATCH_F(F, (bin_scatter_ride_kernel<kF, true, TT><<<ride_grid, block, smem, s>>>(j, VERTEX_RIDE_ARGS))));
   }
@@ -2145,11 +2221,15 @@ extern "C" int gngf_vertex_grid_fwd(const void* tables, int feat_dtype, const in
                                     const int32_t* n_ls_host, float* G, int Ls, int F, int64_t T, int K, int mode,
                                     int vstride, int64_t NV, void* stream) {
   GNGF_CHECK_ARG(Ls > 0 && Ls <= GNGF_MAX_LEVELS && T > 0 && tables && n_ls && n_ls_host && G);
-  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0));
+  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || mode == GNGF_MODE_DENSE_HASH ||
+                 (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0));
   const int side = max_grid_side(n_ls_host, Ls);
   dim3 grid((unsigned)ceil_div((int64_t)side * side, 256), (unsigned)Ls), block(256);
   const bool pow2 = (T & (T - 1)) == 0;
-  if (mode == GNGF_MODE_HASH) {
+  if (mode == GNGF_MODE_DENSE_HASH) {
+    DISPATCH_TT(feat_dtype, DISPATCH_F(F, (vertex_dense_hash_kernel<kF, TT, false><<<grid, block, 0, as_stream(stream)>>>(
+                                static_cast<const TT*>(tables), n_ls, G, nullptr, nullptr, T, pow2))));
+  } else if (mode == GNGF_MODE_HASH) {
     DISPATCH_TT(feat_dtype, DISPATCH_F(F, (vertex_fwd_kernel<kF, false, TT><<<grid, block, 0, as_stream(stream)>>>(
                                 static_cast<const TT*>(tables), nullptr, nullptr, n_ls, G, T, 0, 0, 0, pow2))));
   } else {
@@ -2164,12 +2244,18 @@ extern "C" int gngf_vertex_grid_bwd(const void* tables, int feat_dtype, const in
                                     const int32_t* n_ls_host, const float* dG, float* dtables, float* dvert_w, int Ls, int F,
                                     int64_t T, int K, int mode, int vstride, int64_t NV, void* stream) {
   GNGF_CHECK_ARG(Ls > 0 && Ls <= GNGF_MAX_LEVELS && T > 0 && tables && n_ls && n_ls_host && dG && dtables);
-  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0));
+  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || mode == GNGF_MODE_DENSE_HASH ||
+                 (vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0));
   int64_t vtot = 0;
   for (int l = 0; l < Ls; ++l) vtot += (int64_t)(n_ls_host[l] + 2) * (n_ls_host[l] + 2);
   dim3 grid((unsigned)ceil_div(vtot, 256)), block(256);
   const bool pow2 = (T & (T - 1)) == 0;
-  if (mode == GNGF_MODE_HASH) {
+  if (mode == GNGF_MODE_DENSE_HASH) {
+    const int side = max_grid_side(n_ls_host, Ls);
+    const dim3 lgrid((unsigned)ceil_div((int64_t)side * side, 256), (unsigned)Ls);
+    DISPATCH_TT(feat_dtype, DISPATCH_F(F, (vertex_dense_hash_kernel<kF, TT, true><<<lgrid, block, 0, as_stream(stream)>>>(
+                                static_cast<const TT*>(tables), n_ls, nullptr, dG, dtables, T, pow2))));
+  } else if (mode == GNGF_MODE_HASH) {
     DISPATCH_TT(feat_dtype, DISPATCH_F(F, (vertex_bwd_kernel<kF, false, TT><<<grid, block, 0, as_stream(stream)>>>(
                                 static_cast<const TT*>(tables), nullptr, nullptr, n_ls, dG, dtables, nullptr, Ls, T, 0, 0, 0, pow2))));
   } else {
@@ -2300,6 +2386,7 @@ extern "C" int gngf_encode_tiled_fwd_fused(const float* sorted, const int32_t* i
                                            int K, int mode, int vstride, int64_t NV, int tile_shift, int lds_bytes,
                                            const gngf_bin_job* next_count, void* stream) {
   GNGF_CHECK_ARG(max_items >= 0 && L > 0 && Ls > 0 && Ls <= L && L <= GNGF_MAX_LEVELS && lds_bytes >= 0 && lds_bytes <= 128 * 1024);
+  GNGF_CHECK_ARG(mode != GNGF_MODE_DENSE_HASH);           // (no fused vertex forward for that source: vertex riders + gngf_encode_tiled_fwd)
   BinJobDev cride = bin_job_none();
   GNGF_CHECK_ARG(!next_count || bin_job_dev(next_count, true, &cride));
   if (max_items == 0 && !next_count) return 0;

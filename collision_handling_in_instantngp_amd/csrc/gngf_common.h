@@ -28,6 +28,24 @@ __device__ __forceinline__ int64_t spatial_hash(int gx, int gy, int64_t T, bool 
   return r < 0 ? r + T : r;
 }
 
+// "Row of vertex (gx, gy) of a level whose vertex grid is gw = N_l + 2 wide": the policy (template parameter ROWS) of the kernels
+// that index the level tables without a vertex table.  HashRows is GNGF_MODE_HASH: every level hashed.  DenseHashRows is
+// GNGF_MODE_DENSE_HASH (the Instant-NGP rule): a level whose whole grid fits the table, gw^2 <= T, is indexed one-to-one in the
+// vertex-grid layout — gx, gy clamped to the grid, so a stray coordinate never leaves the level's first gw^2 rows — and only a
+// finer level is hashed.  The branch exists in the DenseHashRows instantiations only.
+struct HashRows {
+  static __device__ __forceinline__ int64_t row(int gx, int gy, int /*gw*/, int64_t T, bool pow2) { return spatial_hash(gx, gy, T, pow2); }
+};
+struct DenseHashRows {
+  static __device__ __forceinline__ bool dense(int gw, int64_t T) { return gw > 0 && (int64_t)gw * gw <= T; }
+  static __device__ __forceinline__ int64_t row(int gx, int gy, int gw, int64_t T, bool pow2) {
+    if (!dense(gw, T)) return spatial_hash(gx, gy, T, pow2);
+    gx = gx < 0 ? 0 : (gx > gw - 1 ? gw - 1 : gx);
+    gy = gy < 0 ? 0 : (gy > gw - 1 ? gw - 1 : gy);
+    return (int64_t)gy * gw + gx;
+  }
+};
+
 // Per-(pixel, level) cell: _scale_to_grid (models.py:486-502) + the coefficients of _bilinear_interpolate
 // (models.py:632-637).  Every operation is a separately rounded fp32 op, as in the reference (compile with
 // -ffp-contract=off).

@@ -25,6 +25,9 @@ namespace gngf {
 
 constexpr int kRenderCols = 16, kRenderRows = 8;        // the workgroup's block; a wave renders 8 x 4 of it
 constexpr int kSrcHash = 0, kSrcTable = 1, kSrcGrid = 2;  // where a corner's features come from
+// GNGF_MODE_DENSE_HASH: the hash source's gather with DenseHashRows (gngf_common.h) for the row — in a dense level the pixels of a
+// wave's 8 x 4 block read neighbouring rows of the level's first (N_l + 2)^2, as the grid source does; a finer level is hashed
+constexpr int kSrcDenseHash = 3;
 
 struct RenderArgs {
   const void* tables; const int32_t* vert_idx; const float* vert_w; const int32_t* n_ls;
@@ -99,7 +102,8 @@ __device__ __forceinline__ void render_issue(RenderGroup& G, const RenderArgs& a
         }
       }
     }
-  } else if constexpr (SRC == kSrcHash) {
+  } else if constexpr (SRC == kSrcHash || SRC == kSrcDenseHash) {
+    using ROWS = typename std::conditional<SRC == kSrcDenseHash, DenseHashRows, HashRows>::type;
 #pragma unroll
     for (int lv = 0; lv < NLG; ++lv) {
       const int level = lev0 + lv;
@@ -109,13 +113,14 @@ __device__ __forceinline__ void render_issue(RenderGroup& G, const RenderArgs& a
         for (int f = 0; f < F; ++f) G.fv[v][lv * F + f] = 0.f;
       G.sx[lv] = G.sy[lv] = 0.f;
       if (EXACT || level < a.L) {
-        const Cell cell = scaled_cell(x, y, a.n_ls[level], G.sx[lv], G.sy[lv]);
+        const int n = a.n_ls[level];
+        const Cell cell = scaled_cell(x, y, n, G.sx[lv], G.sy[lv]);
         const TT* tab = tables + (int64_t)level * a.T * F;
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
           const int gx = cell.gx + (v & 1), gy = cell.gy + (v >> 1);
           float o[F];
-          row_load<F>(tab + spatial_hash(gx, gy, a.T, a.pow2) * F, o);
+          row_load<F>(tab + ROWS::row(gx, gy, n + 2, a.T, a.pow2) * F, o);
 #pragma unroll
           for (int f = 0; f < F; ++f) G.fv[v][lv * F + f] = o[f];
         }
@@ -355,6 +360,10 @@ template <int KIN, typename TT> static RenderKern render_pick(bool leaky, bool e
   if (exact) return vt ? render_kernel<KIN, false, true, kSrcTable, TT> : render_kernel<KIN, false, true, kSrcHash, TT>;
   return vt ? render_kernel<KIN, false, false, kSrcTable, TT> : render_kernel<KIN, false, false, kSrcHash, TT>;
 }
+template <int KIN, typename TT> static RenderKern render_pick_dense_hash(bool leaky, bool exact) {
+  if (leaky) return exact ? render_kernel<KIN, true, true, kSrcDenseHash, TT> : render_kernel<KIN, true, false, kSrcDenseHash, TT>;
+  return exact ? render_kernel<KIN, false, true, kSrcDenseHash, TT> : render_kernel<KIN, false, false, kSrcDenseHash, TT>;
+}
 using RenderGridKern = void (*)(const RenderArgs, const RenderGridArgs);
 template <int KIN> static RenderGridKern render_pick_grid(bool leaky, bool exact) {
   if (leaky) return exact ? render_kernel<KIN, true, true, kSrcGrid, float> : render_kernel<KIN, true, false, kSrcGrid, float>;
@@ -373,7 +382,7 @@ extern "C" int gngf_render(const void* tables, int feat_dtype, const int32_t* ve
   GNGF_CHECK_ARG(L > 0 && L <= GNGF_MAX_LEVELS && (F == 1 || F == 2 || F == 4) && L * F <= 64 && T > 0);
   GNGF_CHECK_ARG(out_dim > 0 && out_dim <= 4);
   GNGF_CHECK_ARG(rows >= 1 && cols >= 1 && denom > 0.f && r0 >= -kExact && c0 >= -kExact && r0 + rows <= kExact && c0 + cols <= kExact);
-  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || mode == GNGF_MODE_VERTEX_TABLE);
+  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || mode == GNGF_MODE_VERTEX_TABLE || mode == GNGF_MODE_DENSE_HASH);
   GNGF_CHECK_ARG(feat_dtype == GNGF_FEAT_F32 || feat_dtype == GNGF_FEAT_F16);
   GNGF_CHECK_ARG(tables && n_ls && W0 && b0 && W1 && b1 && W2 && b2 && (rgb || img));
   GNGF_CHECK_ARG((reinterpret_cast<uintptr_t>(tables) & 15) == 0);
@@ -392,7 +401,10 @@ extern "C" int gngf_render(const void* tables, int feat_dtype, const int32_t* ve
   const size_t smem = sizeof(float) * (size_t)raw_offsets(in_dim).total;
   const bool f16 = feat_dtype == GNGF_FEAT_F16;
   RenderKern fn;
-  if (in_dim <= 32) fn = f16 ? render_pick<32, __half>(leaky != 0, in_dim == 32, vt) : render_pick<32, float>(leaky != 0, in_dim == 32, vt);
+  if (mode == GNGF_MODE_DENSE_HASH) {
+    if (in_dim <= 32) fn = f16 ? render_pick_dense_hash<32, __half>(leaky != 0, in_dim == 32) : render_pick_dense_hash<32, float>(leaky != 0, in_dim == 32);
+    else fn = f16 ? render_pick_dense_hash<64, __half>(leaky != 0, in_dim == 64) : render_pick_dense_hash<64, float>(leaky != 0, in_dim == 64);
+  } else if (in_dim <= 32) fn = f16 ? render_pick<32, __half>(leaky != 0, in_dim == 32, vt) : render_pick<32, float>(leaky != 0, in_dim == 32, vt);
   else fn = f16 ? render_pick<64, __half>(leaky != 0, in_dim == 64, vt) : render_pick<64, float>(leaky != 0, in_dim == 64, vt);
   fn<<<dim3(grid), dim3(kDecThreads), smem, as_stream(stream)>>>(a, RenderNoGrid{});
   GNGF_RETURN_LAUNCH();

@@ -191,16 +191,23 @@ class GeneralNeuralGaugeFields(nn.Module):
         dense_probs      (default 'auto') materialise the (P,L,4,T) distribution when it fits DENSE_OUTPUT_LIMIT_BYTES
         coord_bounds     (default None)  (max_row, max_col) of the coordinates if known: skips one device sync/step
         compute_pbar     (default True)  when probs is returned compact, also reduce the batch-mean distribution
+    dense_levels (constructor keyword, extension; hash indexing only): the index source of the Instant-NGP paper — a level whose
+    whole vertex grid fits the table, (N_l + 2)^2 <= T, is indexed one-to-one (row gy (N_l + 2) + gx: no collisions), only finer
+    levels are hashed (ops.MODE_DENSE_HASH; dense_level_mask says which).  Coordinates must lie in [0, 1]^2.
     """
 
     def __init__(self, input_dim, hash_table_size: int, num_levels: int, n_min: int, n_max: int,
                  MLP_hidden_layers_widths: list, HPD_hidden_layers_widths: list, HPD_out_features: int = 1,
                  feature_dim: int = 2, topk_k: int = 4, should_keep_topk_only: bool = False, should_bw: bool = False,
                  should_log: bool = False, HPD_weights_path: str = None, encoding_weights_path: str = None,
-                 table_dtype: torch.dtype = torch.float32):
+                 table_dtype: torch.dtype = torch.float32, dense_levels: bool = False):
         super().__init__()
         if input_dim != 2:
             raise ValueError("the gfx950 path implements the reference's 2-D image case (input_dim == 2)")
+        if dense_levels and not should_use_hash_function:
+            raise ValueError("dense_levels replaces the spatial hash where a level fits the table: it needs should_use_hash_function")
+        if dense_levels and should_batchnorm_data:
+            raise ValueError("dense_levels indexes the vertices of [0, 1]^2; should_batchnorm_data moves the coordinates out of it")
         self._hash_table_size = hash_table_size
         self._num_levels = num_levels
         self._n_min = n_min
@@ -238,6 +245,9 @@ class GeneralNeuralGaugeFields(nn.Module):
             for i in range(len(widths) - 1)
         ])
         self._hash_mode = bool(should_use_hash_function)
+        self._dense_levels = bool(dense_levels)
+        # [level l is indexed one-to-one]: all False without dense_levels
+        self.dense_level_mask = (ops.dense_level_mask(self._n_ls_host, hash_table_size) if dense_levels else [False] * num_levels)
         self._leaky = bool(should_leaky_relu)
         self.return_indices = True
         self.dense_probs = "auto"
@@ -385,6 +395,15 @@ class GeneralNeuralGaugeFields(nn.Module):
             if self._hash_mode:
                 vs = self._n_max + 2
                 self._mark_reachable_rows(None, vs, vs * vs)
+                if self._dense_levels:
+                    # the dense levels' rows [0, (N_l + 2)^2) ORed on top of the hashed ones (the marking kernel serves the spatial
+                    # hash only): a superset of what the model addresses, which is all gngf_adam_step_masked needs
+                    bit = torch.arange(self._row_map.shape[1] * 32, device=dev)
+                    weight = torch.tensor([1 << k for k in range(32)], dtype=torch.int64, device=dev)
+                    for l, dense in enumerate(self.dense_level_mask):
+                        if dense:
+                            words = ((bit < (self._n_ls_host[l] + 2) ** 2).view(-1, 32).to(torch.int64) * weight).sum(1)
+                            self._row_map[l] |= torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
         if frozen is not None:
             _tv, ti, _w, vstride, NV, _order = self._frozen_vertex_table(frozen)      # (marks when it has to rebuild)
             if fresh:
@@ -394,6 +413,8 @@ class GeneralNeuralGaugeFields(nn.Module):
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor, batch_percentage: float = 1.0, should_calc_counts: bool = False):
         if should_batchnorm_data:
+            if self._dense_levels:
+                raise ValueError("dense_levels indexes the vertices of [0, 1]^2; should_batchnorm_data moves the coordinates out of it")
             x = self._batch_norm(x)
         x = x.contiguous()
         dev = x.device
@@ -416,12 +437,14 @@ class GeneralNeuralGaugeFields(nn.Module):
         if self._hash_mode:
             # batch-normalised coordinates (models.py:394-397) leave [0,1]^2: the direct form hashes any integer vertex
             enc = ops.encode_apply(x, n_ls, self._n_ls_host, tables, None, None, 0, path=("direct" if should_batchnorm_data else None),
-                                   dp=dp, link=link, sink=sink)
+                                   dp=dp, link=link, sink=sink, **({"mode": ops.MODE_DENSE_HASH} if self._dense_levels else {}))
             rgb = self._decode(enc, link)
             if self.track_collisions and not should_batchnorm_data:
                 vs = self._n_max + 2
                 self._mark_batch_slots(x.detach(), n_ls, None, vs, vs * vs)
             idx = ops.hash_indices(x.detach(), n_ls, T) if (self.return_indices or should_calc_counts) else None
+            if idx is not None and self._dense_levels:
+                self._dense_rows_into(idx, x.detach(), n_ls)
             counts = self._calc_counts_per_level(idx, x.detach(), n_ls) if should_calc_counts else []
             return rgb, None, idx, counts
 
@@ -469,6 +492,22 @@ class GeneralNeuralGaugeFields(nn.Module):
             to_return_probs = VertexDistribution((P, L, 4, T), pbar, tv)
         counts = self._calc_counts_per_level(idx64[..., 0], x.detach(), n_ls) if should_calc_counts else []
         return rgb, to_return_probs, idx64, counts
+
+    @torch.no_grad()
+    def _dense_rows_into(self, idx, x, n_ls):
+        """Overwrites the dense levels of a hash-source index tensor (P,L,4) with the rows those levels use: gy (N_l + 2) + gx
+        of corner v = dx + 2 dy, gx / gy clamped to the grid as the kernels clamp them (torch: part of the reference-shaped
+        return contract, not of the hot path)."""
+        nf = n_ls.to(torch.float32)
+        g = torch.floor(x[:, :, None] * nf[None, None, :]).to(torch.int64)                  # (P,2,L): _scale_to_grid, fp32 product
+        hi = (n_ls.to(torch.int64) + 1)[None, :]
+        for v in range(4):
+            gx = torch.minimum((g[:, 0] + (v & 1)).clamp_min(0), hi)
+            gy = torch.minimum((g[:, 1] + (v >> 1)).clamp_min(0), hi)
+            rows = gy * (hi + 1) + gx                                                           # (P,L)
+            for l, dense in enumerate(self.dense_level_mask):
+                if dense:
+                    idx[:, l, v] = rows[:, l]
 
     def _forward_per_instance(self, x, n_ls, link, should_calc_counts):
         """GNGF indexing on coordinates outside [0,1]^2 (should_batchnorm_data, models.py:394-397: BatchNorm1d output is
@@ -579,6 +618,9 @@ class GeneralNeuralGaugeFields(nn.Module):
         per epoch; the maps accumulate over the batches in between (a trainable HPD changes the per-vertex table from batch to
         batch: each batch marks with its own, as the reference's per-batch indices do, functions.py:211-216, 327)."""
         from ._lib import query
+        if self._dense_levels:
+            raise RuntimeError("collision tracking marks the spatial hash's slots (gngf_mark_batch_slots has no index-source argument): "
+                               "a dense_levels model reports collisions from its returned indices (calc_hash_collisions)")
         L, T = self._num_levels, self._hash_table_size
         K = 1 if self._hash_mode else self._topk_k
         dev = self.encoding._hash_tables[0].weight.device

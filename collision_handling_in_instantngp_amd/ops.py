@@ -14,6 +14,8 @@ from ._lib import call, ptr, query, stream_ptr
 
 BLEND_CODES = {True: 0, None: 1, False: 2}   # should_softmax_topk_features -> GNGF_BLEND_*
 MODE_HASH, MODE_VERTEX_TABLE = 0, 1
+# GNGF_MODE_DENSE_HASH (include/gngf.h): level l is indexed one-to-one, row gy * (N_l + 2) + gx, when (N_l + 2)^2 <= T; else hashed
+MODE_DENSE_HASH = 2
 MAX_TOPK = 128        # GNGF_MAX_TOPK_WIDE: the largest K any entry point takes
 MAX_TOPK_LIST = 32    # GNGF_MAX_TOPK: above it the selection, blend and module-boundary kernels are those of csrc/topk_wide.hip
 
@@ -24,6 +26,25 @@ def check_topk(K):
     if K > MAX_TOPK:
         raise ValueError(f"topk_k = {K} exceeds the limit of {MAX_TOPK} (ops.MAX_TOPK, GNGF_MAX_TOPK_WIDE)")
     return K
+
+
+def index_source(vert_idx, mode=None):
+    """The GNGF_MODE_* of an encoder call.  The callers say it explicitly (`mode`); None keeps the old reading of the arguments:
+    the spatial hash without a vertex table, the vertex table with one."""
+    if mode is None:
+        return MODE_HASH if vert_idx is None else MODE_VERTEX_TABLE
+    mode = int(mode)
+    if mode not in (MODE_HASH, MODE_VERTEX_TABLE, MODE_DENSE_HASH):
+        raise ValueError(f"index source {mode}: not one of MODE_HASH, MODE_VERTEX_TABLE, MODE_DENSE_HASH")
+    if (mode == MODE_VERTEX_TABLE) != (vert_idx is not None):
+        raise ValueError("a vertex table goes with MODE_VERTEX_TABLE, and with no other index source")
+    return mode
+
+
+def dense_level_mask(n_ls_host, T):
+    """[level l is dense under MODE_DENSE_HASH: (N_l + 2)^2 <= T] — the kernels' own rule (csrc/gngf_common.h: DenseHashRows)"""
+    return [(int(n) + 2) ** 2 <= int(T) for n in n_ls_host]
+
 
 _f32, _i32, _i64 = torch.float32, torch.int32, torch.int64
 
@@ -347,11 +368,11 @@ class EncodeDirectFunction(torch.autograd.Function):
     vert_w (NV,K) fp32 blend weights; the gradient returned for vert_w is dL/dw (before the blend's backward)."""
 
     @staticmethod
-    def forward(ctx, xy, n_ls, tables, vert_idx, vert_w, vstride):
+    def forward(ctx, xy, n_ls, tables, vert_idx, vert_w, vstride, mode=None):
         xy, tables = _c(xy), _c(tables)
         L, T, F = tables.shape
         P = xy.shape[0]
-        mode = MODE_HASH if vert_idx is None else MODE_VERTEX_TABLE
+        mode = index_source(vert_idx, mode)
         K = check_topk(0 if vert_idx is None else vert_idx.shape[1])
         NV = 0 if vert_idx is None else vert_idx.shape[0]
         enc = torch.empty((P, L * F), dtype=_f32, device=tables.device)
@@ -370,7 +391,7 @@ class EncodeDirectFunction(torch.autograd.Function):
         dtables = _grad_buffer(tables)
         dvw = torch.zeros_like(vert_w) if (vert_w is not None and ctx.needs_input_grad[4]) else None
         _direct_bwd(xy, tables, vert_idx, vert_w, n_ls, genc, dtables, dvw, P, L, F, T, K, mode, vstride, NV, 0, L)
-        return None, None, _grad_out(dtables, tables), None, dvw, None
+        return None, None, _grad_out(dtables, tables), None, dvw, None, None
 
 
 # ------------------------------------------------------------------------------------------------ dense layers
@@ -1215,7 +1236,7 @@ def _drop_bin_workspace(dev, ntiles, owner=None):
 class TiledWorkspace:
     """Device buffers of one forward/backward pair (binning result is shared by both)."""
 
-    def __init__(self, plan, xy, vertex=None, zero_dG=None, zero=None, zero_dG_words=1, owner=None, launch=True, clear_rows=None):
+    def __init__(self, plan, xy, vertex=None, zero_dG=None, zero=None, zero_dG_words=1, owner=None, launch=True, clear_rows=None, mode=None):
         """vertex = (tables, vert_idx, vert_w, n_ls, vstride, G): also run the vertex stage forward into G (riding on the binning
         launches); zero_dG (same shape as G) and zero (any fp32 buffer, typically the table gradient): cleared on the way.
         launch=False: buffers only (filled by bin2(), or by another step's riders through job())."""
@@ -1238,7 +1259,7 @@ class TiledWorkspace:
             # binning + vertex stage forward + the clears of the backward's gradient buffers: one chain of four launches
             tables, vert_idx, vert_w, n_ls, vstride, G = vertex
             L, T, F = tables.shape
-            mode = MODE_HASH if vert_idx is None else MODE_VERTEX_TABLE
+            mode = index_source(vert_idx, mode)
             if zero is not None and (zero.numel() % 4 or zero.data_ptr() % 16 or zero.dtype != _f32):
                 zero.zero_()
                 zero = None
@@ -1248,7 +1269,7 @@ class TiledWorkspace:
                      *_tab(tables), ptr(vert_idx), ptr(vert_w), ptr(n_ls), plan.n_ls_c, ptr(G), ptr(zero_dG), int(zero_dG_words), plan.Ls, F, T,
                      0 if vert_idx is None else vert_idx.shape[1], mode, vstride, 0 if vert_idx is None else vert_idx.shape[0],
                      ptr(zero), 0 if zero is None else zero.numel(), ptr(_bin_workspace(dev, plan.ntiles, owner)),
-                     ptr(clear_rows if vert_idx is None else None, _f32, "clear_rows"), stream_ptr())
+                     ptr(clear_rows if mode == MODE_HASH else None, _f32, "clear_rows"), stream_ptr())
             except Exception:
                 # the count launch may have run without the scatter launch that puts the persistent counters back to zero: the
                 # next step gets a fresh (zeroed) workspace instead of binning with dirty totals
@@ -1265,9 +1286,9 @@ def _bin_job(ws, plan, xy, pws):
     return job
 
 
-def _vertex_fwd(plan, tables, vert_idx, vert_w, n_ls, vstride, G):
+def _vertex_fwd(plan, tables, vert_idx, vert_w, n_ls, vstride, G, mode=None):
     L, T, F = tables.shape
-    mode = MODE_HASH if vert_idx is None else MODE_VERTEX_TABLE
+    mode = index_source(vert_idx, mode)
     call("gngf_vertex_grid_fwd", *_tab(tables), ptr(vert_idx), ptr(vert_w), ptr(n_ls), plan.n_ls_c, ptr(G), plan.Ls, F, T,
          0 if vert_idx is None else vert_idx.shape[1], mode, vstride, 0 if vert_idx is None else vert_idx.shape[0], stream_ptr())
 
@@ -1499,7 +1520,7 @@ def _flat_list_of(order, plan, vert_idx, vert_w, T):
     return lists.get(plan.Ls, vert_idx, vert_w, T)
 
 
-def _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw, order=None, dG64=None, flat=None):
+def _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw, order=None, dG64=None, flat=None, mode=None):
     """dG64: the fixed-point vertex grid of _pixel_bwd(..., dG=None, dG64=...) read directly (slot-ordered and flat forms only).
     flat: the VertexFlatList of this (frozen) table for levels [0, plan.Ls) — without d w the flat segmented reduction runs."""
     L, T, F = tables.shape
@@ -1516,7 +1537,7 @@ def _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw,
         return
     if dG64 is not None:
         raise ValueError("the fixed-point vertex grid is read by the slot-ordered vertex backward only")
-    mode = MODE_HASH if vert_idx is None else MODE_VERTEX_TABLE
+    mode = index_source(vert_idx, mode)
     call("gngf_vertex_grid_bwd", *_tab(tables), ptr(vert_idx), ptr(vert_w), ptr(n_ls), plan.n_ls_c, ptr(dG), ptr(dtables), ptr(dvw),
          plan.Ls, F, T, 0 if vert_idx is None else vert_idx.shape[1], mode, vstride,
          0 if vert_idx is None else vert_idx.shape[0], stream_ptr())
@@ -1550,7 +1571,7 @@ class StepConfig:
     DEMOTE the planned chain to the general one (partial images + gather pass, zeroed allocations): EncodeFunction.backward decides
     those fallbacks in one place, and they are traced too (PIXEL_BWD_TRACE records, the "table_grad" record of STEP_TRACE).
     tests/test_step_config_cpu.py enumerates the reachable configurations and names the GPU parity test that runs each."""
-    source: str            # "hash" | "vertex_table"
+    source: str            # "hash" | "vertex_table" | "dense_hash"
     staged: int            # levels in the tiled form (plan.Ls); 0: direct form only
     direct: int            # levels in the direct form
     binning: str           # "pipeline": two launches of its own or none (the previous step's riders) | "prepare": rides with the vertex stage | "none"
@@ -1559,7 +1580,7 @@ class StepConfig:
     grad_sink: str         # where the staged levels' backward puts its sums: "table_rows" | "dG64" | "fp32_grid" | "none" (no gradient)
     table_grad: str        # "block" ([dE | grid]: ONE allocation) | "persist" (step-to-step buffer) | "alloc" | "none"
     clear: str             # who clears it: "decoder" (between its MFMAs) | "riders" (of the binning launch) | "rows" (sparse, persist) | "none"
-    direct_bwd: str        # "bucketed_write" | "bucketed_or_atomics" (decided per call on the density) | "none"
+    direct_bwd: str        # "bucketed_write" | "bucketed_or_atomics" (decided per call on the density) | "atomics" (dense_hash) | "none"
     exchange: bool         # a data-parallel exchange of the vertex-grid gradient is set up
     vertex_bwd_flat: bool = False      # vertex-table source: the backward of the vertex stage runs over the frozen table's static item list
 
@@ -1584,9 +1605,26 @@ class StepConfig:
         (zero_hidden: the one-launch training kernel, which clears for free).  persist_alloc_ok: the step-to-step buffer exists or may
         be allocated now (not inside a capture).  have_reserve_ws: the persistent counters of the two-launch binning exist."""
         t = TUNING
-        src = "hash" if mode == MODE_HASH else "vertex_table"
         tiled = plan.Ls > 0 and P > 0
         nd = L - plan.Ls
+        if mode == MODE_DENSE_HASH:
+            # the chain the hash source takes under a data-parallel exchange, on one rank: vertex riders build G (a dense level's
+            # grid is its table's first rows), the pixel stage adds into the grid gradient, gngf_vertex_grid_bwd(mode 2) adds that
+            # to the tables.  No fused vertex forward, no table-row sink, no step-to-step buffer, no bucketed direct backward (all
+            # four are written for the spatial hash alone); direct levels add with atomics.
+            if exchange:
+                raise ValueError("the dense-where-it-fits index source does not run under a data-parallel exchange")
+            dbw = "atomics" if (needs_grad and nd > 0) else "none"
+            if not tiled:
+                return StepConfig("dense_hash", 0, L, "none", "none", "none", "none", "alloc" if needs_grad else "none", "none", dbw, False)
+            il = plan.interleaved(backward=bool(needs_grad))
+            if not needs_grad:
+                return StepConfig("dense_hash", plan.Ls, nd, "prepare", "riders", "interleaved" if il else "generic", "none", "none", "none",
+                                  "none", False)
+            return StepConfig("dense_hash", plan.Ls, nd, "prepare", "riders", "interleaved" if il else "generic",
+                              "dG64" if (F == 2 and plan.Ls <= 16 and il) else "fp32_grid", "alloc",
+                              "decoder" if link_defer_zero else "riders", dbw, False)
+        src = "hash" if mode == MODE_HASH else "vertex_table"
         if not tiled:       # (direct form only: a data-parallel exchange changes nothing in the encoder's own chain)
             return StepConfig(src, 0, L, "none", "none", "none", "none", "alloc" if needs_grad else "none", "none",
                               "bucketed_or_atomics" if (needs_grad and nd > 0) else "none", False)
@@ -1633,12 +1671,12 @@ class EncodeFunction(torch.autograd.Function):
     EncodeDirectFunction (reference models.py:486-528, 173-229, 621-655 and their autograd backward)."""
 
     @staticmethod
-    def forward(ctx, xy, n_ls, plan, tables, vert_idx, vert_w, vstride, order=None, dp=None, link=None, sink=None):
+    def forward(ctx, xy, n_ls, plan, tables, vert_idx, vert_w, vstride, order=None, dp=None, link=None, sink=None, mode=None):
         ctx.dp, ctx.link, ctx.sink = dp, link, sink
         xy, tables = _c(xy), _c(tables)
         L, T, F = tables.shape
         P = xy.shape[0]
-        mode = MODE_HASH if vert_idx is None else MODE_VERTEX_TABLE
+        mode = index_source(vert_idx, mode)
         K = check_topk(0 if vert_idx is None else vert_idx.shape[1])
         NV = 0 if vert_idx is None else vert_idx.shape[0]
         enc = torch.empty((P, L * F), dtype=_f32, device=tables.device)
@@ -1744,7 +1782,7 @@ class EncodeFunction(torch.autograd.Function):
                 ws = TiledWorkspace(plan, xy, vertex=(tables, vert_idx, vert_w, n_ls, vstride, G),
                                     zero_dG=None if dgrid is None else (dgrid.view(_f32) if use64 else dgrid),
                                     zero=(zbuf if (zbuf is not None and not defer) else None),
-                                    zero_dG_words=(2 if use64 else 1), owner=dp, clear_rows=clear_now)
+                                    zero_dG_words=(2 if use64 else 1), owner=dp, clear_rows=clear_now, mode=mode)
                 if gather:
                     call("gngf_encode_tiled_fwd_fused", ptr(ws.sorted), ptr(ws.items), ptr(ws.n_items), plan.max_items, ptr(n_ls), plan.n_ls_c,
                          *_tab(tables), ptr(None), ptr(None), ptr(enc), L, plan.Ls, F, T, 0, mode, 0, 0, plan.tile_shift, plan.lds_bytes, None,
@@ -1775,7 +1813,7 @@ class EncodeFunction(torch.autograd.Function):
             dp.tables_reduced = 0
             dp.deferred = None
         exchange = dp.exchange if dp is not None else None
-        NONE = (None,) * 5                                      # (order, dp, link, sink) + vstride: no gradients
+        NONE = (None,) * 6                                      # (order, dp, link, sink, mode) + vstride: no gradients
         buf, ctx.buffers = ctx.buffers, None                    # a second backward (retain_graph) allocates fresh buffers
         if buf is not None and buf.zbuf is not None and link is not None and link.zero_request is buf.zbuf:
             link.zero_request = None                            # the decoder that was to clear the buffer did not run: clear it here
@@ -1802,7 +1840,7 @@ class EncodeFunction(torch.autograd.Function):
         dvw = torch.zeros_like(vert_w) if (vert_w is not None and ctx.needs_input_grad[5]) else None
         if plan.Ls > 0 and P > 0:
             # hash source, single rank: the vertex stage backward rides on the pixel stage (its store pass or its gather pass)
-            fuse = (dtables, T) if (vert_idx is None and exchange is None) else None
+            fuse = (dtables, T) if (mode == MODE_HASH and exchange is None) else None
             # sink "table_rows": the pixel stage — level-interleaved or generic kernel, with or without a bound on |d enc| — adds
             # to the table gradient itself
             direct_hash = grad_sink == "table_rows" and fuse is not None
@@ -1848,8 +1886,9 @@ class EncodeFunction(torch.autograd.Function):
             else:
                 dvw_t = None
                 # (the frozen table's static item list, when the forward pass found one: the flat segmented reduction)
+                # (the index source is named only where the arguments do not already say it: the dense-where-it-fits source)
                 _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw, order, dG64 if direct64 else None,
-                            **({"flat": ctx.flat} if ctx.flat is not None else {}))
+                            **({"mode": mode} if mode == MODE_DENSE_HASH else {}), **({"flat": ctx.flat} if ctx.flat is not None else {}))
         else:
             dvw_t = None
         if plan.Ls < L:
@@ -1860,12 +1899,12 @@ class EncodeFunction(torch.autograd.Function):
         return (None, None, None, _grad_out(dtables, tables, sink), None, dvw, *NONE)
 
 
-def encode_apply(xy, n_ls, n_ls_host, tables, vert_idx, vert_w, vstride, path=None, order=None, dp=None, link=None, sink=None):
+def encode_apply(xy, n_ls, n_ls_host, tables, vert_idx, vert_w, vstride, path=None, order=None, dp=None, link=None, sink=None, mode=None):
     """Fused encoder dispatch: tiled form for the levels it can stage, direct form for the rest.
     order: optional cached slot_order(vert_idx) (frozen tables); dp: the model's DataParallel state; link: the forward
-    pass's StepLink (shared with decoder_apply); sink: see table_view()."""
+    pass's StepLink (shared with decoder_apply); sink: see table_view(); mode: the index source (index_source)."""
     plan = EncodePlan(xy.shape[0], n_ls_host, tables.shape[2], path)
-    return EncodeFunction.apply(xy, n_ls, plan, tables, vert_idx, vert_w, vstride, order, dp, link, sink)
+    return EncodeFunction.apply(xy, n_ls, plan, tables, vert_idx, vert_w, vstride, order, dp, link, sink, mode)
 
 
 _MSE_WORKSPACE = {}
@@ -2009,11 +2048,12 @@ def snapshot_if(table, nrec, total_blocks, flag):
 
 
 def render_lattice(tables, n_ls, decoder_params, rows, cols, denom, origin=(0, 0), *, vert_idx=None, vert_w=None, vstride=0,
-                   leaky=False, out_rgb=None, out_image=None):
+                   leaky=False, out_rgb=None, out_image=None, mode=None):
     """The model on the lattice ((r0 + r) / denom, (c0 + c) / denom), r < rows, c < cols, in one forward-only launch
     (csrc/render.inc: gngf_render; include/gngf.h has the contract).  tables (L,T,F) fp32 | fp16, n_ls (L) int32,
     decoder_params [W0, b0, W1, b1, W2, b2]; vert_idx / vert_w (NV,K) and vstride select the vertex-table source, None the
-    spatial hash.  out_rgb (rows cols, C) fp32 and / or out_image (same shape) int32 are written; at least one is needed.
+    spatial hash — or, with mode=MODE_DENSE_HASH, the dense-where-it-fits source (index_source).
+    out_rgb (rows cols, C) fp32 and / or out_image (same shape) int32 are written; at least one is needed.
     No autograd, no workspace, no allocation, no synchronisation — and no StepConfig: this is not a step of training."""
     L, T, F = tables.shape
     W0, b0, W1, b1, W2, b2 = decoder_params
@@ -2036,17 +2076,18 @@ def render_lattice(tables, n_ls, decoder_params, rows, cols, denom, origin=(0, 0
     call("gngf_render", tp, code, ptr(vert_idx, _i32, "vert_idx"), ptr(vert_w, _f32, "vert_w"), ptr(n_ls, _i32, "n_ls"),
          ptr(W0, _f32, "W0"), ptr(b0, _f32, "b0"), ptr(W1, _f32, "W1"), ptr(b1, _f32, "b1"), ptr(W2, _f32, "W2"), ptr(b2, _f32, "b2"),
          ptr(out_rgb, _f32, "out_rgb"), ptr(out_image, _i32, "out_image"), int(rows), int(cols), int(origin[0]), int(origin[1]),
-         float(denom), L, F, T, K, MODE_VERTEX_TABLE if vt else MODE_HASH, int(vstride), NV, C, int(bool(leaky)), stream_ptr())
+         float(denom), L, F, T, K, index_source(vert_idx, mode), int(vstride), NV, C, int(bool(leaky)), stream_ptr())
 
 
 def _grid_vertices(n_ls_host):
     return sum((int(n) + 2) ** 2 for n in n_ls_host)
 
 
-def bake_vertex_grid(tables, n_ls, n_ls_host, vert_idx, vert_w, vstride, NV, F, T, K, out=None):
+def bake_vertex_grid(tables, n_ls, n_ls_host, vert_idx, vert_w, vstride, NV, F, T, K, out=None, mode=None):
     """The vertex grid of EVERY level for the current tables: G (sum_l (N_l + 2)^2, F) fp32 with
     G[goff_l + gy (N_l + 2) + gx] = sum_k vert_w[v, k] tables[l, vert_idx[v, k]] (v = gy vstride + gx; vert_idx None: the row
-    spatial_hash(gx, gy) itself) — gngf_vertex_grid_fwd with Ls = L, the vertex stage of a training step.  tables (L,T,F)
+    spatial_hash(gx, gy) itself, or under mode=MODE_DENSE_HASH row gy (N_l + 2) + gx of a level that fits) —
+    gngf_vertex_grid_fwd with Ls = L, the vertex stage of a training step.  tables (L,T,F)
     fp32 | fp16, n_ls (L) int32 and its host mirror, vert_idx / vert_w (NV,K).  out: the grid to write instead of a new one.
     No autograd, no StepConfig: this is not a step of training."""
     L = len(n_ls_host)
@@ -2064,7 +2105,7 @@ def bake_vertex_grid(tables, n_ls, n_ls_host, vert_idx, vert_w, vstride, NV, F, 
         raise ValueError(f"out holds {out.numel()} elements for a grid of {vtot} x {F}")
     call("gngf_vertex_grid_fwd", *_tab(tables), ptr(vert_idx, _i32, "vert_idx"), ptr(vert_w, _f32, "vert_w"), ptr(n_ls, _i32, "n_ls"),
          (_ct.c_int32 * L)(*[int(n) for n in n_ls_host]), ptr(out, _f32, "out"), L, int(F), int(T), K,
-         MODE_VERTEX_TABLE if vt else MODE_HASH, int(vstride) if vt else 0, int(NV) if vt else 0, stream_ptr())
+         index_source(vert_idx, mode), int(vstride) if vt else 0, int(NV) if vt else 0, stream_ptr())
     return out
 
 
@@ -2347,12 +2388,12 @@ def decoder_apply(enc, acts, params, fused=None, mse_target=None, mse_gloss=None
 
 
 # ------------------------------------------------------------------------------------------------ per-kernel launch closures
-def encode_kernels(xy, n_ls, n_ls_host, tables, vert_idx, vert_w, vstride, genc, path=None):
+def encode_kernels(xy, n_ls, n_ls_host, tables, vert_idx, vert_w, vstride, genc, path=None, mode=None):
     """{name: zero-arg launcher} for the encoder kernels the current dispatch uses (bench.py times each one alone
     with HIP events on the launch stream)."""
     L, T, F = tables.shape
     P = xy.shape[0]
-    mode = MODE_HASH if vert_idx is None else MODE_VERTEX_TABLE
+    mode = index_source(vert_idx, mode)
     K = check_topk(0 if vert_idx is None else vert_idx.shape[1])
     NV = 0 if vert_idx is None else vert_idx.shape[0]
     enc = torch.empty((P, L * F), dtype=_f32, device=xy.device)
@@ -2363,11 +2404,11 @@ def encode_kernels(xy, n_ls, n_ls_host, tables, vert_idx, vert_w, vstride, genc,
     if plan.Ls > 0:
         G = torch.empty((plan.vtot, F), dtype=_f32, device=xy.device)
         dG = torch.zeros_like(G)
-        ws = TiledWorkspace(plan, xy, vertex=(tables, vert_idx, vert_w, n_ls, vstride, G))     # as the training step does (pixels sorted inside the items)
+        ws = TiledWorkspace(plan, xy, vertex=(tables, vert_idx, vert_w, n_ls, vstride, G), mode=mode)     # as the training step does (pixels sorted inside the items)
         am = genc.abs().max().reshape(1)
-        out["prepare"] = lambda: TiledWorkspace(plan, xy, vertex=(tables, vert_idx, vert_w, n_ls, vstride, G), zero_dG=dG, zero=dtables)
+        out["prepare"] = lambda: TiledWorkspace(plan, xy, vertex=(tables, vert_idx, vert_w, n_ls, vstride, G), zero_dG=dG, zero=dtables, mode=mode)
         out["bin_pixels"] = lambda: TiledWorkspace(plan, xy)
-        out["vertex_fwd"] = lambda: _vertex_fwd(plan, tables, vert_idx, vert_w, n_ls, vstride, G)
+        out["vertex_fwd"] = lambda: _vertex_fwd(plan, tables, vert_idx, vert_w, n_ls, vstride, G, mode)
         out["encode_fwd:tiled"] = lambda: call("gngf_encode_tiled_fwd", ptr(ws.sorted), ptr(ws.items), ptr(ws.n_items),
                                                plan.max_items, ptr(n_ls), plan.n_ls_c, ptr(G), ptr(enc), L, plan.Ls, F,
                                                plan.tile_shift, plan.lds_bytes, s())
@@ -2380,7 +2421,7 @@ def encode_kernels(xy, n_ls, n_ls_host, tables, vert_idx, vert_w, vstride, genc,
                 dG64.zero_()                    # (the training step clears it in rider workgroups of the binning launch)
                 _pixel_bwd(plan, ws, n_ls, genc, dG, L, F, (am, 1, 0), None, None, dG64)
             out["encode_bwd:tiled+dG64"] = bwd64
-        out["vertex_bwd"] = lambda: _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, None, order)
+        out["vertex_bwd"] = lambda: _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, None, order, mode=mode)
     if plan.Ls < L:
         out["encode_fwd:direct"] = lambda: call("gngf_encode_fwd", ptr(xy), *_tab(tables), ptr(vert_idx), ptr(vert_w), ptr(n_ls),
                                                 ptr(enc), P, L, F, T, K, mode, vstride, NV, plan.Ls, L, ptr(None), s())

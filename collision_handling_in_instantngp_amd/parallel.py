@@ -33,6 +33,9 @@ def enable_vertex_grid_exchange(net, world: int, group=None):
     dG -> dE is linear and identical on every rank, so reducing dG first gives the same table gradient with ~11x
     fewer bytes on the xGMI links.  Levels that run in the direct form (the finest levels of very fine grids) keep the
     table-gradient exchange, restricted to their own contiguous slice of the (L,T,F) buffer."""
+    if world > 1 and getattr(net, "_dense_levels", False):
+        raise ValueError("a dense_levels model does not run under a data-parallel exchange (the deferred vertex stage and the "
+                         "collision marking serve the spatial hash and the vertex table only)")
     dp = net.dp
     dp.tables_reduced = 0              # bookkeeping of a previous configuration does not carry over
     dp.deferred = None

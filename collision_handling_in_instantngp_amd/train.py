@@ -750,8 +750,9 @@ def train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_coll
     one = torch.ones((), device=dev)                 # seed of backward(): the same d loss / d loss = 1, without a fill per batch
     # the reference's collision statistic (functions.py:327) without the index tensor: when the model does not return indices the
     # forward passes mark the slots their batches use (models.start_collision_tracking) and train_step reads the maps
+    # (a dense_levels model cannot track — the marking kernel serves the spatial hash only: the statistic comes from its indices)
     tracked = (hasattr(net, "start_collision_tracking") and not getattr(net, "return_indices", True) and not should_calc_counts
-               and not models.should_batchnorm_data)
+               and not models.should_batchnorm_data and not getattr(net, "_dense_levels", False))
     if tracked:
         net.start_collision_tracking()
     elif hasattr(net, "stop_collision_tracking"):
@@ -1330,6 +1331,13 @@ def _check_unit_square(rows, cols, r0, c0, denom, why):
         raise ValueError(f"{why} over [0, 1]^2; this lattice spans [{r0 / float(d):g}, {float(hi):g}]" + _GENERAL_PATH)
 
 
+def _index_source(net):
+    """the ops.MODE_* a model's encoder runs with"""
+    if not net._hash_mode:
+        return ops.MODE_VERTEX_TABLE
+    return ops.MODE_DENSE_HASH if getattr(net, "_dense_levels", False) else ops.MODE_HASH
+
+
 def _render_setup(net, rows, cols, denom, origin):
     """Validation shared by render(): (rows, cols, r0, c0, denom, C) or ValueError naming net(x) as the general path."""
     if denom is None:
@@ -1338,6 +1346,8 @@ def _render_setup(net, rows, cols, denom, origin):
     C = _check_render_model(net, "render()")
     if not net._hash_mode:
         _check_unit_square(rows, cols, r0, c0, denom, "render(): GNGF indexing looks vertices up in the table")
+    elif getattr(net, "_dense_levels", False):
+        _check_unit_square(rows, cols, r0, c0, denom, "render(): a dense level clamps a vertex outside its grid, so the model is defined")
     return rows, cols, r0, c0, float(np.float32(denom)), C
 
 
@@ -1396,7 +1406,8 @@ def render(net, rows, cols, denom=None, origin=(0, 0), *, rgb=True, image=False,
     if not net._hash_mode:
         ti, w, vstride = _render_vertex_table(net)
     ops.render_lattice(tables, net._n_ls_flat(dev), [p.detach() for p in net._decoder_params()], rows, cols, denom, (r0, c0),
-                       vert_idx=ti, vert_w=w, vstride=vstride, leaky=net._leaky, out_rgb=out_rgb, out_image=out_image)
+                       vert_idx=ti, vert_w=w, vstride=vstride, leaky=net._leaky, out_rgb=out_rgb, out_image=out_image,
+                       mode=_index_source(net))
     if out_rgb is not None and out_image is not None:
         return out_rgb, out_image
     return out_rgb if out_rgb is not None else out_image
@@ -1525,7 +1536,7 @@ def bake(net, *, out=None):
     if not net._hash_mode:
         ti, w, vstride = _render_vertex_table(net)
         NV, K = int(ti.shape[0]), int(ti.shape[1])
-    ops.bake_vertex_grid(tables, out.n_ls, n_ls_host, ti, w, vstride, NV, F, T, K, out=out.grid)
+    ops.bake_vertex_grid(tables, out.n_ls, n_ls_host, ti, w, vstride, NV, F, T, K, out=out.grid, mode=_index_source(net))
     for d, s in zip(out.decoder, dec):
         d.copy_(s)
     return out

@@ -40,8 +40,19 @@ enum { GNGF_BLEND_SOFTMAX = 0 /* True */, GNGF_BLEND_RAW = 1 /* None */, GNGF_BL
 /* storage type of the level tables: fp32 (the reference) or fp16 (BASELINE.json config 5); arithmetic and gradients are fp32 */
 enum { GNGF_FEAT_F32 = 0, GNGF_FEAT_F16 = 1 };
 
-/* index source of the fused encoder */
-enum { GNGF_MODE_HASH = 0 /* models.py:412-414 */, GNGF_MODE_VERTEX_TABLE = 1 /* models.py:416-418, de-duplicated */ };
+/* index source of the fused encoder.
+ * GNGF_MODE_DENSE_HASH (additive: no ABI version of its own) is the rule of the Instant-NGP paper: level l is DENSE when its whole
+ * vertex grid fits the table, (N_l + 2)^2 <= T, and vertex (gx, gy) then uses row gy * (N_l + 2) + gx — the vertex-grid layout, so
+ * G_l is the first (N_l + 2)^2 rows of the level's table and no two vertices share a row; gx and gy are clamped to [0, N_l + 1]
+ * there, so a coordinate outside [0, 1]^2 never leaves those rows.  Any other level uses spatial_hash(gx, gy, T) as
+ * GNGF_MODE_HASH does.  vert_idx / vert_w / K / vstride / NV are ignored, as for GNGF_MODE_HASH; feature types and F as the entry
+ * point supports for GNGF_MODE_HASH.  Accepted by gngf_encode_fwd, gngf_encode_bwd, gngf_vertex_grid_fwd, gngf_vertex_grid_bwd,
+ * gngf_encode_tiled_prepare (G required; clear_rows rejected) and gngf_render; REJECTED (hipErrorInvalidValue) by
+ * gngf_encode_tiled_fwd_fused — the staged levels take gngf_encode_tiled_prepare + gngf_encode_tiled_fwd, and their backward
+ * gngf_encode_tiled_bwd into dG (without hash_dtables) + gngf_vertex_grid_bwd.  The entry points without a mode argument
+ * (gngf_encode_bwd_bucketed, gngf_clear_hashed_rows, gngf_mark_batch_slots, gngf_hash_indices) serve the spatial hash only. */
+enum { GNGF_MODE_HASH = 0 /* models.py:412-414 */, GNGF_MODE_VERTEX_TABLE = 1 /* models.py:416-418, de-duplicated */,
+       GNGF_MODE_DENSE_HASH = 2 /* dense where it fits, hashed elsewhere */ };
 
 int gngf_abi_version(void);
 
@@ -64,7 +75,7 @@ int gngf_bilinear_bwd(const float* xy, const int32_t* n_ls, const float* genc, f
 
 /* ---- a5..a12 fused, "direct" form: one lane per (pixel, level); table rows gathered straight from HBM/L2.
  * Only levels [l0, l1) are produced / consumed (enc rows stay (P, L*F)); the tiled form below covers the others.
- * mode HASH: vert_idx/vert_w NULL, K ignored.
+ * mode HASH, DENSE_HASH: vert_idx/vert_w NULL, K ignored (DENSE_HASH: the backward adds to the dense rows with atomics too).
  * mode VERTEX_TABLE: vert_idx (NV,K) int32 slots and vert_w (NV,K) blend weights per grid vertex
  *   (vid = gy*vstride + gx), i.e. HPD(top-K) evaluated once per DISTINCT vertex instead of per instance.
  * pixel_order (ABI 12, may be NULL): as in gngf_encode_bwd_bucketed — the pixels walked in the tiled form's binned order (the
@@ -137,7 +148,10 @@ int gngf_encode_tiled_prepare(const float* xy, int64_t P, int tile_shift, int NB
 int gngf_vertex_grid_fwd(const void* tables, int feat_dtype, const int32_t* vert_idx, const float* vert_w, const int32_t* n_ls,
                          const int32_t* n_ls_host, float* G, int Ls, int F, int64_t T, int K, int mode, int vstride,
                          int64_t NV, void* stream);
-/* dG -> dtables (L,T,F) accumulated (caller zero-fills) and dvert_w (NV,K) accumulated (NULL when not needed). */
+/* dG -> dtables (L,T,F) accumulated (caller zero-fills) and dvert_w (NV,K) accumulated (NULL when not needed).
+ * GNGF_MODE_DENSE_HASH (both directions): a dense level is a copy / an add of its (N_l + 2)^2 F consecutive values, 16 bytes per
+ * lane where the level's bases are 16-byte aligned (no atomics: launches that add to the same dtables rows must be ordered on
+ * the stream); rows >= (N_l + 2)^2 of a dense level are not touched. */
 int gngf_vertex_grid_bwd(const void* tables, int feat_dtype, const int32_t* vert_idx, const float* vert_w, const int32_t* n_ls,
                          const int32_t* n_ls_host, const float* dG, float* dtables, float* dvert_w, int Ls, int F, int64_t T,
                          int K, int mode, int vstride, int64_t NV, void* stream);
@@ -516,7 +530,7 @@ int gngf_image_metrics(const int32_t* img, const uint8_t* target, int64_t* sums,
  *   rgb (rows cols, out_dim) fp32 = decoder(encoding(coordinate)), the forward pass of gngf_encode_fwd + gngf_decoder_fwd
  *   without the (P, L F) encoding in memory; img (same shape) int32 = (int32)(rgb * 255.0f), gngf_image_scatter's
  *   quantisation.  Either may be NULL, not both.  No workspace, no synchronisation.
- * tables (L,T,F) of feat_dtype, 16-byte aligned; mode GNGF_MODE_HASH, or GNGF_MODE_VERTEX_TABLE with vert_idx / vert_w
+ * tables (L,T,F) of feat_dtype, 16-byte aligned; mode GNGF_MODE_HASH, GNGF_MODE_DENSE_HASH, or GNGF_MODE_VERTEX_TABLE with vert_idx / vert_w
  * (NV,K), vstride and NV as gngf_encode_fwd takes them (vertices outside the table are clamped; NV K < 2^31).
  * Decoder W0 (64, L F), W1 (64,64), W2 (out_dim,64) and biases, hidden activation ReLU or (leaky) LeakyReLU(0.01).
  * Requires F in {1,2,4}, L <= GNGF_MAX_LEVELS, L F <= 64, out_dim <= 4, rows, cols >= 1, denom > 0 and
