@@ -107,6 +107,15 @@ SIGNATURES = {
 
 ABI_VERSION = 15
 
+# include/gngf.h is closed at ABI 15.  Entry points added since live in include/gngf_ext.h, in the same library, with a version of
+# their own: name -> argtypes, mirroring that header exactly.
+EXT_SIGNATURES = {
+    "gngf_ext_version": [],
+    "gngf_ext_sample_pixels": [_P, _L, _L, _I, _F, _L, _P, _I, _P, _P, _L, _P],
+}
+
+EXT_VERSION = 1
+
 
 class BinJob(ctypes.Structure):
     """include/gngf.h: gngf_bin_job — one binning job as a host struct (passed by pointer: ctypes.byref)."""
@@ -132,7 +141,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C collision_handling_in_instantngp_amd/csrc`.  There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -142,6 +151,9 @@ def load():
     ver = lib.gngf_abi_version()
     if ver != ABI_VERSION:
         raise GngfLibraryError(f"ABI version mismatch: library {ver}, binding {ABI_VERSION}")
+    ext = lib.gngf_ext_version()
+    if ext != EXT_VERSION:
+        raise GngfLibraryError(f"extension version mismatch (include/gngf_ext.h): library {ext}, binding {EXT_VERSION}")
     _lib = lib
     return lib
 

@@ -4,6 +4,8 @@ written against it finds the same names and conventions:
   MyDataset            utils.py:12-75      image file -> (X, Y, height, width); X = integer (row, col) pixel list in
                                            row-major order, Y = channels / 255
   normalise / permutation                  main.py:50-58: x / (max(w, h) - 1); shuffled_indices and their inverse
+  ImageSampler                             (no counterpart) training batches drawn on the device from the uint8 image itself:
+                                           random continuous positions with bilinear targets, or random pixel centres
   reassemble_image     functions.py:308,332-335: inverse permutation, (output * 255) -> int32 image (truncation)
   reassemble_image_device                  the same image as a device tensor, written by the scatter kernel
   save_checkpoint / load_checkpoint        functions.py:761-781, models.py HPD/encoding weight paths: the five
@@ -11,8 +13,9 @@ written against it finds the same names and conventions:
   save_snapshot                            the same five files from the best state train.fit kept on the device
   save_baked / load_baked                  a train.BakedGrid (vertex grids + decoder: the picture without the model) as one file
 
-Host-side numpy/torch only, with one exception: reassemble_image_device runs the image scatter kernel (csrc/metrics.hip,
-through ops.image_scatter) and needs device tensors."""
+Host-side numpy/torch only, with two exceptions: reassemble_image_device runs the image scatter kernel (csrc/metrics.hip,
+through ops.image_scatter) and needs device tensors, and ImageSampler lives on the device (csrc/sample.hip, through
+ops.sample_pixels)."""
 import os
 from typing import Optional, Tuple
 
@@ -93,6 +96,80 @@ def make_permutation(shape: int, generator: Optional[torch.Generator] = None) ->
     reordered = torch.zeros((shape,)).int()
     reordered[shuffled.long()] = torch.arange(shape).int()
     return shuffled, reordered
+
+
+class ImageSampler:
+    """Training batches drawn on the device from the uint8 image itself (ops.sample_pixels, csrc/sample.hip) — the image task of
+    Instant-NGP: `batch` random positions per draw, continuous (targets looked up bilinearly) or pixel centres with replacement.
+    The image, 1 B per pixel and channel, is the only per-pixel storage: no coordinate tensor, no target tensor, no permutation.
+
+        sampler = ImageSampler(img, 2 ** 18)             # img: uint8 (h,w) | (h,w,C <= 4), numpy or a device tensor
+        x, target = sampler.next()                       # (batch,2) fp32 (row, col) / denom and (batch,C) fp32
+
+    next() returns views of one of `buffers` rotating pairs: a batch stays valid for buffers - 1 further draws.  It does not
+    allocate and does not synchronise (capturable: the draw counter lives on the device, every replay draws a new batch).
+    coord_bounds: an upper bound of the coordinates of every batch (GraphedStep's coord_bounds)."""
+
+    def __init__(self, image, batch: int, *, seed: int = 0, continuous: bool = True, denom: Optional[float] = None,
+                 device="cuda", buffers: int = 2) -> None:
+        img = torch.as_tensor(image)
+        if img.dtype != torch.uint8:
+            raise TypeError(f"image must be uint8, got {img.dtype}")
+        if img.dim() == 2:
+            img = img.unsqueeze(-1)
+        if img.dim() != 3 or not 1 <= img.shape[2] <= 4:
+            raise ValueError(f"image must be (h, w) or (h, w, C <= 4), got {tuple(img.shape)}")
+        self.h, self.w, self.C = (int(s) for s in img.shape)
+        self.batch, self.seed, self.continuous = int(batch), int(seed), bool(continuous)
+        if self.batch < 1 or int(buffers) < 1:
+            raise ValueError("batch and buffers must be at least 1")
+        if self.h < 1 or self.w < 1 or (self.continuous and (self.h < 2 or self.w < 2)):
+            raise ValueError(f"a {self.h} x {self.w} image cannot be sampled" + (" continuously" if self.continuous else ""))
+        if denom is None:
+            denom = max(self.h, self.w) - 1
+        self.denom = float(denom)
+        if not self.denom > 0:
+            raise ValueError(f"denom must be > 0, got {self.denom} (a 1 x 1 image needs an explicit denom)")
+        self.image = img.to(device).contiguous()
+        dev = self.image.device
+        self._draw = torch.zeros((), dtype=torch.int64, device=dev)
+        self._pairs = [(torch.empty((self.batch, 2), dtype=torch.float32, device=dev),
+                        torch.empty((self.batch, self.C), dtype=torch.float32, device=dev)) for _ in range(int(buffers))]
+        self.buffers = len(self._pairs)
+        self._turn = 0
+        # the largest coordinates any draw can give, in the kernel's own fp32 arithmetic
+        f32 = np.float32
+        self.coord_bounds = (float(f32(self.h - 1) / f32(self.denom)), float(f32(self.w - 1) / f32(self.denom)))
+
+    def next(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        from . import ops
+        x, target = self._pairs[self._turn]
+        self._turn = (self._turn + 1) % len(self._pairs)
+        ops.sample_pixels(self.image, self.seed, self._draw, x, target, denom=self.denom, continuous=self.continuous)
+        # written in place behind torch's back: whoever keys a cache on (address, version) — the binning pipeline — must see it
+        torch.autograd.graph.increment_version(x)
+        torch.autograd.graph.increment_version(target)
+        return x, target
+
+    @property
+    def draw(self) -> int:
+        """the number of batches drawn so far (reads the device counter: synchronises)"""
+        return int(self._draw.item())
+
+    def data_bytes(self) -> int:
+        """device bytes of the data side: the image, the batch buffers and the counter"""
+        return (self.image.numel() + 8 + sum(x.numel() * 4 + t.numel() * 4 for x, t in self._pairs))
+
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "draw": self.draw, "batch": self.batch, "mode": "continuous" if self.continuous else "pixel"}
+
+    def load_state_dict(self, state: dict) -> None:
+        """continues the sequence of draws of a sampler of the same batch size and mode (the draws depend on both)"""
+        mode = "continuous" if self.continuous else "pixel"
+        if int(state["batch"]) != self.batch or state["mode"] != mode:
+            raise ValueError(f"state of a sampler with batch {state['batch']}, mode {state['mode']!r}; this one has {self.batch}, {mode!r}")
+        self.seed = int(state["seed"])
+        self._draw.fill_(int(state["draw"]))
 
 
 def reassemble_image(outputs: torch.Tensor, reordered_indices: Optional[torch.Tensor], h: int, w: int,

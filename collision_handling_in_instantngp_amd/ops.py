@@ -2047,6 +2047,44 @@ def snapshot_if(table, nrec, total_blocks, flag):
     call("gngf_snapshot_if", ptr(table, torch.uint8, "table"), int(nrec), int(total_blocks), ptr(flag, _i32, "flag"), stream_ptr())
 
 
+SAMPLE_MAX_SIDE = 1 << 24        # include/gngf_ext.h: the generator gives 24 bits per axis
+
+
+def sample_pixels(image, seed, draw, xy, target, *, denom, continuous):
+    """One training batch drawn from the uint8 image on the device (csrc/sample.hip: gngf_ext_sample_pixels; include/gngf_ext.h has
+    the generator and the arithmetic to the bit).  image (h,w,C) uint8, C <= 4; draw: one device int64, the number of batches drawn
+    so far — read by the launch, raised by one behind it; xy (P,2) and target (P,C) fp32 are written.  continuous False: random
+    pixel centres with replacement; True: random positions with bilinear targets.  Everything is checked here, before any device
+    work; no allocation, no synchronisation: capturable."""
+    if image.dim() != 3:
+        raise ValueError(f"image must be (h, w, C), got {tuple(image.shape)}")
+    h, w, C = (int(s) for s in image.shape)
+    if not 1 <= C <= 4:
+        raise ValueError(f"image has {C} channels: 1..4 are supported")
+    if not (1 <= h <= SAMPLE_MAX_SIDE and 1 <= w <= SAMPLE_MAX_SIDE):
+        raise ValueError(f"image sides must lie in [1, 2^24], got {h} x {w}")
+    continuous = bool(continuous)
+    if continuous and (h < 2 or w < 2):
+        raise ValueError(f"continuous sampling interpolates between texels: the image needs two rows and two columns, got {h} x {w}")
+    denom = float(denom)
+    if not denom > 0:
+        raise ValueError(f"denom must be > 0, got {denom}")
+    if xy.dim() != 2 or xy.shape[1] != 2:
+        raise ValueError(f"xy must be (P, 2), got {tuple(xy.shape)}")
+    P = int(xy.shape[0])
+    if tuple(target.shape) != (P, C):
+        raise ValueError(f"target must be (P, C) = ({P}, {C}), got {tuple(target.shape)}")
+    if draw.numel() != 1:
+        raise ValueError("draw is one device int64")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    seed = seed - (1 << 64) if seed >= (1 << 63) else seed          # the same 64 bits as a signed argument
+    args = (ptr(image, torch.uint8, "image"), h, w, C, denom, seed, ptr(draw, _i64, "draw"), int(continuous),
+            ptr(xy, _f32, "xy"), ptr(target, _f32, "target"), P, stream_ptr())
+    if P == 0:
+        return
+    call("gngf_ext_sample_pixels", *args)
+
+
 def render_lattice(tables, n_ls, decoder_params, rows, cols, denom, origin=(0, 0), *, vert_idx=None, vert_w=None, vstride=0,
                    leaky=False, out_rgb=None, out_image=None, mode=None):
     """The model on the lattice ((r0 + r) / denom, (c0 + c) / denom), r < rows, c < cols, in one forward-only launch

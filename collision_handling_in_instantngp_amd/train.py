@@ -824,6 +824,71 @@ def train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_coll
     return rec
 
 
+def train_sampled(net, loss_fn, optimizer, sampler, steps, *, l_mse, l_js_kl, l_collisions, graph=True, previous_collisions=None,
+                  previous_min_possible_collisions=None):
+    """`steps` optimisation steps on batches a data.ImageSampler draws on the device from the image itself (random positions, or
+    random pixel centres) — no coordinate tensor, no target tensor, no permutation.  Batch k + 1 is drawn before step k runs and
+    named to it, so a replayed step (graph=True: GraphedStep with the sampler's coord_bounds and cross_replay, cached on the net)
+    bins its successor's pixels and none but the first bins at its head; an eager step (graph=False) is train_epoch's.  The call
+    advances sampler.draw by steps + 1: the batch drawn ahead of the last step is not trained on (the next call draws its own).
+    Returns {"loss": (steps,), "mse": (steps,)} fp32 device tensors; nothing is read back to the host.  Scoring stays with
+    render_psnr(net, og_image).  Hash, dense_levels and GNGF models (frozen or trainable HPD); not should_batchnorm_data (the
+    sampler's coordinates are the unit square's) and not with a data-parallel exchange (the ranks would draw the same batches)."""
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    if models.should_batchnorm_data:
+        raise ValueError("train_sampled: should_batchnorm_data moves the coordinates out of the unit square the sampler draws in")
+    dp = getattr(net, "dp", None)
+    if dp is not None and (dp.active or dp.defer_vertex or dp.world > 1 or dp.zero is not None):
+        raise ValueError("train_sampled: every rank of a data-parallel exchange would draw the same batches; sharded draws are not built")
+    if sampler.buffers < 2:
+        raise ValueError("train_sampled draws batch k + 1 while batch k is in use: the sampler needs buffers >= 2")
+    net.train()
+    dev = sampler.image.device
+    empty = torch.tensor([], device=dev)
+    previous_collisions = empty if previous_collisions is None else previous_collisions.to(dev)
+    previous_min_possible_collisions = empty if previous_min_possible_collisions is None else previous_min_possible_collisions.to(dev)
+    losses = torch.zeros((steps,), device=dev)
+    mses = torch.zeros((steps,), device=dev)
+    if steps == 0:
+        return {"loss": losses, "mse": mses}
+    if hasattr(net, "stop_collision_tracking"):
+        net.stop_collision_tracking()
+    gs = None
+    if graph:
+        gs = getattr(net, "_graphed_step", None)
+        cfg = (id(loss_fn), id(optimizer), l_mse, l_js_kl, l_collisions, 1.0, False, "sampled", tuple(sampler.coord_bounds))
+        if gs is None or gs._cfg != cfg:
+            gs = GraphedStep(net, loss_fn, optimizer, l_mse, l_js_kl, l_collisions, 1.0, coord_bounds=sampler.coord_bounds,
+                             cross_replay=True)
+            gs._cfg = cfg
+            net._graphed_step = gs
+    one = torch.ones((), device=dev)
+    pipe = getattr(dp, "pipeline", None)
+    upcoming = sampler.next()
+    for k in range(steps):
+        bx, by = upcoming
+        upcoming = sampler.next()                    # batch k + 1, in the other buffer pair: batch k stays as it is
+        if gs is not None:
+            r = gs(bx, by, previous_collisions, previous_min_possible_collisions, next_first=upcoming[0])
+            loss, mse = r.loss, r.mse
+        else:
+            if pipe is not None:
+                pipe.announce(upcoming[0] if k + 1 < steps else None)
+            optimizer.zero_grad()
+            with (net.fused_mse(by, gloss=promised_gloss(loss_fn, l_mse)) if hasattr(net, "fused_mse") else contextlib.nullcontext()):
+                out, probs, _idx, _counts = net(bx, 1.0, should_calc_counts=False)
+            mse, kls, colls = loss_fn(out, by, None if probs is None else probs.shape[-1], probs,
+                                      previous_collisions, previous_min_possible_collisions)
+            loss = assemble_loss(mse, kls, colls, l_mse, l_js_kl, l_collisions)
+            loss.backward(gradient=one.to(loss.dtype))
+            optimizer.step()
+        losses[k].copy_(loss.detach())
+        mses[k].copy_(mse.detach())
+    return {"loss": losses, "mse": mses}
+
+
 def train_step(net, loss_fn, optimizer, x, target, w, h, hash_table_size, topk_k, l_mse, l_js_kl, l_collisions,
                batch_percentage=1, num_levels=4, should_bw=False, should_calc_counts=False, should_shuffle=True,
                shuffled_indices=None, reordered_indices=None, previous_collisions=None,
