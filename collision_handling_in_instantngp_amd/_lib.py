@@ -116,6 +116,17 @@ EXT_SIGNATURES = {
 
 EXT_VERSION = 1
 
+# include/gngf_ext.h is closed as well (two names, version 1).  include/gngf_ext2.h is the open one: a new entry point is added
+# there and here, and GNGF_EXT2_VERSION / EXT2_VERSION rise together.
+EXT2_SIGNATURES = {
+    "gngf_ext2_version": [],
+    "gngf_ext2_render_score_workspace_words": [],
+    "gngf_ext2_render_score": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _I, _L, _I, _I,
+                               _P, _L, _L, _I, _F, _L, _P, _P, _P],
+}
+
+EXT2_VERSION = 1
+
 
 class BinJob(ctypes.Structure):
     """include/gngf.h: gngf_bin_job — one binning job as a host struct (passed by pointer: ctypes.byref)."""
@@ -141,7 +152,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C collision_handling_in_instantngp_amd/csrc`.  There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, argtypes in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(EXT2_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -154,6 +165,9 @@ def load():
     ext = lib.gngf_ext_version()
     if ext != EXT_VERSION:
         raise GngfLibraryError(f"extension version mismatch (include/gngf_ext.h): library {ext}, binding {EXT_VERSION}")
+    ext2 = lib.gngf_ext2_version()
+    if ext2 != EXT2_VERSION:
+        raise GngfLibraryError(f"extension version mismatch (include/gngf_ext2.h): library {ext2}, binding {EXT2_VERSION}")
     _lib = lib
     return lib
 

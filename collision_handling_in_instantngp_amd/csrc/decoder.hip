@@ -35,16 +35,9 @@
 #include <type_traits>
 #include <utility>
 
+#include "decoder_common.inc"   // f32x16 / f32x4, kH, kDecThreads, crow / kmapC, MFMA, raw_offsets / stage_raw (shared with render.inc)
+
 namespace gngf {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-constexpr int kH = 64;                 // hidden width (both hidden layers)
-constexpr int kDecThreads = 256;
-
-__device__ __forceinline__ int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-// k index (feature of a 64-wide activation held as two accumulator tiles) consumed at chained k-step s2 by lane half h
-__device__ __forceinline__ int kmapC(int s2, int h) { return 32 * (s2 >> 4) + crow(s2 & 15, h); }
 
 // One VALU instruction for ReLU (fmaxf compiles to a canonicalising v_max pair), two for LeakyReLU (max(z, 0.01 z)).
 // On gfx950 a wave's VALU instructions do NOT overlap its MFMAs (measured: 64 + 10 + 4n cycles for an MFMA followed by
@@ -88,7 +81,7 @@ template <typename F, int... I> __device__ __forceinline__ void static_for_impl(
 }
 template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+// MFMA (decoder_common.inc) is the builtin.
 // The same MFMA with its accumulator tile in ARCHITECTURAL VGPRs (hipcc's builtin always selects the AGPR form in a
 // 512-register kernel, and every VALU touch of an AGPR result costs a v_accvgpr_read): used for the tiles whose results
 // go straight through VALU (activations, masks).  Inline asm is invisible to the hazard recogniser, so the one hazard
@@ -101,27 +94,6 @@ template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
 #define MFMA_VV_ZERO(acc, a, b) asm("v_mfma_f32_32x32x2_f32 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b))
 #define MFMA_DRAIN(x, y) asm volatile("s_nop 15\n\ts_nop 2" : "+v"(x), "+v"(y))
 #define MFMA_DRAIN1(x) asm volatile("s_nop 15\n\ts_nop 2" : "+v"(x))
-
-// Coalesced copy of the raw weights into LDS with a +1 padded row stride (conflict-free strided reads afterwards):
-//   W0s [64][in_dim+1] | W1s [64][65] | W2s [4][65] | b0 [64] | b1 [64] | b2 [4]
-struct RawOff { int w0, w1, w2, b0, b1, b2, total; };
-__host__ __device__ inline RawOff raw_offsets(int in_dim) {
-  RawOff o;
-  o.w0 = 0; o.w1 = o.w0 + kH * (in_dim + 1); o.w2 = o.w1 + kH * 65; o.b0 = o.w2 + 4 * 65; o.b1 = o.b0 + kH; o.b2 = o.b1 + kH;
-  o.total = o.b2 + 4;
-  return o;
-}
-__device__ __forceinline__ void stage_raw(float* raw, const float* __restrict__ W0, const float* __restrict__ b0,
-                                          const float* __restrict__ W1, const float* __restrict__ b1,
-                                          const float* __restrict__ W2, const float* __restrict__ b2, int in_dim, int out_dim) {
-  const RawOff o = raw_offsets(in_dim);
-  for (int e = threadIdx.x; e < kH * in_dim; e += kDecThreads) raw[o.w0 + (e / in_dim) * (in_dim + 1) + e % in_dim] = W0[e];
-  for (int e = threadIdx.x; e < kH * kH; e += kDecThreads) raw[o.w1 + (e >> 6) * 65 + (e & 63)] = W1[e];
-  for (int e = threadIdx.x; e < 4 * kH; e += kDecThreads) raw[o.w2 + (e >> 6) * 65 + (e & 63)] = (e >> 6) < out_dim ? W2[e] : 0.f;
-  for (int e = threadIdx.x; e < kH; e += kDecThreads) { raw[o.b0 + e] = b0[e]; raw[o.b1 + e] = b1[e]; }
-  if (threadIdx.x < 4) raw[o.b2 + threadIdx.x] = (b2 && (int)threadIdx.x < out_dim) ? b2[threadIdx.x] : 0.f;
-  __syncthreads();
-}
 
 // LDS fragment images.  frag[(tile * S + s) * 64 + lane].
 template <int KIN>
@@ -152,7 +124,6 @@ __device__ __forceinline__ void fill_fwd_frags(float* A0, float* A1, const float
 // chained through the accumulators, and the 3-4 wide output layer on v_mfma_f32_4x4x1_16b_f32 (16 blocks of 4 pixels:
 // the lane's own accumulator register is the B operand, the lane's (channel = lane%4) weight the A operand; the two
 // lane halves hold different features of the same pixel and are combined with one cross-half shuffle).
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 // Device-clock span of the last decoder_bwd launch: [0] = constant 100 MHz counter when workgroup 0 started, [1] = the latest

@@ -1,5 +1,6 @@
-// Forward-only render of a pixel lattice in ONE launch (included at the end of decoder.hip: it needs that file's local helpers —
-// stage_raw / raw_offsets, crow / kmapC, the MFMA macro and the 4x4x1 output layer with its sigmoid).
+// Forward-only render of a pixel lattice in ONE launch (included at the end of decoder.hip, and by render_score.hip for the
+// scoring forms: it needs decoder_common.inc — stage_raw / raw_offsets, crow / kmapC, the MFMA macro — and repeats the 4x4x1 output
+// layer of decoder_fwd_kernel with its sigmoid).
 //
 // decoder_fwd_kernel with its input produced in place: a lane owns one pixel of the lattice (col = lane & 31 of the transposed
 // products), computes the pixel's coordinate from its row and column — ((float)(r0 + r) / denom, (float)(c0 + c) / denom), one
@@ -21,6 +22,10 @@
 // It holds fewer live values than the other sources: no scratch at 32 features, 8 / 72 spilled registers at 64 (exact / narrower).
 // Registers: the 32-feature forms fit the 512-entry file; the 64-feature forms (64 more weight registers, two groups) spill
 // 28 - 125 registers to scratch in the gather phases.
+// Scoring forms (the kSrc*Score sources, instantiated in render_score.hip: gngf_ext2_render_score): the same pixels by the same
+// operations, but the sink is a comparison — the integer (int32_t)(y * 255.0f) against the uint8 image the lattice was laid over
+// (pixel (i step, j step) of it), accumulated per lane as two exact int64 sums, reduced across the wave, through LDS across the
+// workgroup's waves, and stored as the workgroup's two partial sums.  Nothing of the picture is written.
 namespace gngf {
 
 constexpr int kRenderCols = 16, kRenderRows = 8;        // the workgroup's block; a wave renders 8 x 4 of it
@@ -28,6 +33,10 @@ constexpr int kSrcHash = 0, kSrcTable = 1, kSrcGrid = 2;  // where a corner's fe
 // GNGF_MODE_DENSE_HASH: the hash source's gather with DenseHashRows (gngf_common.h) for the row — in a dense level the pixels of a
 // wave's 8 x 4 block read neighbouring rows of the level's first (N_l + 2)^2, as the grid source does; a finer level is hashed
 constexpr int kSrcDenseHash = 3;
+// The scoring forms: source kSrcScore + s gathers as source s (hash, vertex table, dense-where-it-fits; not the grid) and compares
+// instead of storing.  A source of its own, not a further template parameter: the storing instantiations keep their names.
+constexpr int kSrcScore = 4;
+constexpr int kSrcHashScore = kSrcScore + kSrcHash, kSrcTableScore = kSrcScore + kSrcTable, kSrcDenseHashScore = kSrcScore + kSrcDenseHash;
 
 struct RenderArgs {
   const void* tables; const int32_t* vert_idx; const float* vert_w; const int32_t* n_ls;
@@ -47,6 +56,13 @@ struct RenderGridArgs { const float* grid; int64_t goff[GNGF_MAX_LEVELS]; };
 struct RenderNoGrid {};
 template <int SRC> struct RenderSrcArgs { using type = RenderNoGrid; };
 template <> struct RenderSrcArgs<kSrcGrid> { using type = RenderGridArgs; };
+// the scoring forms' second argument: `image` (h, w, C = out_dim) uint8 is compared at pixel (r step, c step) for the lattice point
+// (r, c), w the image's width; partial[2 b], partial[2 b + 1] = (#equal elements, sum of squared differences) of workgroup b
+// (written by every workgroup: nothing needs clearing)
+struct RenderScore { const uint8_t* image; int64_t w, step; int64_t* partial; };
+template <> struct RenderSrcArgs<kSrcHashScore> { using type = RenderScore; };
+template <> struct RenderSrcArgs<kSrcTableScore> { using type = RenderScore; };
+template <> struct RenderSrcArgs<kSrcDenseHashScore> { using type = RenderScore; };
 
 // one table row (F consecutive values, F sizeof(TT)-aligned: the table base is 16-byte aligned) as fp32 — tload's values
 template <int F> __device__ __forceinline__ void row_load(const float* r, float (&o)[F]) {
@@ -229,6 +245,8 @@ template <int KIN, bool LEAKY, bool EXACT, int SRC, typename TT>
 __global__ void __launch_bounds__(kDecThreads, 1)
 render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
   constexpr int S0 = KIN / 2, NG = S0 / 16;
+  constexpr bool SCORE = SRC >= kSrcScore;                 // ga is the RenderScore sink; a.rows x a.cols its lattice, a.r0 = a.c0 = 0
+  constexpr int GSRC = SCORE ? SRC - kSrcScore : SRC;      // where the corners come from
   const int in_dim = EXACT ? KIN : a.L * a.F;
   const int out_dim = a.out_dim;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
@@ -269,19 +287,38 @@ render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
   const int64_t gq = (int64_t)gridDim.x / nbx, gr = (int64_t)gridDim.x % nbx;
   int64_t by = (int64_t)blockIdx.x / nbx, bx = (int64_t)blockIdx.x % nbx;
   const int lr = (wave >> 1) * 4 + (i >> 3), lc = (wave & 1) * 8 + (i & 7);      // this lane's pixel inside a block
-  // (r0 + rows, c0 + cols <= 2^24: the integers are exact in fp32; lanes past the ragged edges compute and store nothing)
+  // (r0 + rows, c0 + cols <= 2^24: the integers are exact in fp32; lanes past the ragged edges store nothing — in the scoring
+  // forms they compute the last row / column's pixel again and are masked out of the sums)
   auto coord = [&](int64_t brow, int64_t bcol, float& x, float& y) {
-    x = (float)(int)(a.r0 + brow * kRenderRows + lr) / a.denom;
-    y = (float)(int)(a.c0 + bcol * kRenderCols + lc) / a.denom;
+    if constexpr (SCORE) {
+      // image pixel (r step, c step) of lattice point (r, c) — an exact integer < 2^24 — over denom; a lane past a ragged edge
+      // takes the last row / column's coordinate (inside the image, as every gather of the model expects) and adds nothing
+      const int64_t r = brow * kRenderRows + lr, c = bcol * kRenderCols + lc;
+      x = (float)(int)((r < a.rows ? r : a.rows - 1) * ga.step) / a.denom;
+      y = (float)(int)((c < a.cols ? c : a.cols - 1) * ga.step) / a.denom;
+    } else {
+      x = (float)(int)(a.r0 + brow * kRenderRows + lr) / a.denom;
+      y = (float)(int)(a.c0 + bcol * kRenderCols + lc) / a.denom;
+    }
   };
+  [[maybe_unused]] int64_t eq = 0, sse = 0;                 // (scoring forms only)
   float xr[S0], x, y;
   RenderGroup G;
   coord(by, bx, x, y);
-  RENDER_F(render_issue<kF, SRC, EXACT, TT>(G, a, ga, h * (S0 / kF), x, y); render_combine<kF, 0>(G, xr));
+  RENDER_F(render_issue<kF, GSRC, EXACT, TT>(G, a, ga, h * (S0 / kF), x, y); render_combine<kF, 0>(G, xr));
   if constexpr (NG == 2)
-    RENDER_F(render_issue<kF, SRC, EXACT, TT>(G, a, ga, h * (S0 / kF) + 16 / kF, x, y); render_combine<kF, 16>(G, xr));
+    RENDER_F(render_issue<kF, GSRC, EXACT, TT>(G, a, ga, h * (S0 / kF) + 16 / kF, x, y); render_combine<kF, 16>(G, xr));
   for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
     const int64_t pr = by * kRenderRows + lr, pc = bx * kRenderCols + lc;         // this block's pixel
+    [[maybe_unused]] uint32_t tv[4] = {0u, 0u, 0u, 0u};      // scoring forms: the pixel's texels, requested ahead of the MFMA runs
+    if constexpr (SCORE) {
+      // no divergent branch: a lane past a ragged edge reads the last row / column's texel (a valid address) and is masked below
+      const int64_t tr = pr < a.rows ? pr : a.rows - 1, tc = pc < a.cols ? pc : a.cols - 1;
+      const uint8_t* t = ga.image + ((tr * ga.step) * ga.w + tc * ga.step) * (int64_t)out_dim;          // 64-bit offsets
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (c < out_dim) tv[c] = t[c];
+    }
     int64_t nrow = by + gq, ncol = bx + gr;
     if (ncol >= nbx) { ncol -= nbx; ++nrow; }
     if (blk + gridDim.x >= nblocks) { nrow = by; ncol = bx; }                     // past the end: this block again, never used
@@ -298,7 +335,7 @@ render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
       acc1[1] = MFMA(a0r[1][sx], xr[sx], acc1[1]);
     }
     __builtin_amdgcn_sched_barrier(0);
-    RENDER_F(render_issue<kF, SRC, EXACT, TT>(G, a, ga, h * (S0 / kF), x, y));
+    RENDER_F(render_issue<kF, GSRC, EXACT, TT>(G, a, ga, h * (S0 / kF), x, y));
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -313,7 +350,7 @@ render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
     }
     __builtin_amdgcn_sched_barrier(0);
     RENDER_F(render_combine<kF, 0>(G, xr));
-    if constexpr (NG == 2) RENDER_F(render_issue<kF, SRC, EXACT, TT>(G, a, ga, h * (S0 / kF) + 16 / kF, x, y));
+    if constexpr (NG == 2) RENDER_F(render_issue<kF, GSRC, EXACT, TT>(G, a, ga, h * (S0 / kF) + 16 / kF, x, y));
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -337,7 +374,16 @@ render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
         // Sigmoid on the hardware exp2 / rcp units, as decoder_fwd_kernel
         yv[c] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z * -1.4426950408889634f));
       }
-      if (h == 0 && pr < a.rows && pc < a.cols) {
+      if constexpr (SCORE) {
+        const bool mine = h == 0 && pr < a.rows && pc < a.cols;       // the lane that would store this pixel
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (c < out_dim) {                                          // metric_add of csrc/metrics.hip on the integer a render stores
+            const int64_t d = (int64_t)(int32_t)(yv[c] * 255.0f) - (int64_t)tv[c];
+            eq += mine && d == 0;
+            sse += mine ? d * d : 0;
+          }
+      } else if (h == 0 && pr < a.rows && pc < a.cols) {
         const int64_t e = (pr * a.cols + pc) * out_dim;
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -348,8 +394,24 @@ render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
       }
     }
   }
+  if constexpr (SCORE) {
+    // lanes -> wave (shuffles), waves -> workgroup (LDS), one pair per workgroup: integer sums, any split gives the same result
+    __shared__ int64_t red[2][kDecThreads / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { eq += __shfl_xor(eq, o, 64); sse += __shfl_xor(sse, o, 64); }
+    if (lane == 0) { red[0][wave] = eq; red[1][wave] = sse; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+      int64_t s = 0;
+#pragma unroll
+      for (int wv = 0; wv < kDecThreads / 64; ++wv) s += red[threadIdx.x][wv];
+      ga.partial[2 * (int64_t)blockIdx.x + threadIdx.x] = s;
+    }
+  }
 }
 #undef RENDER_F
+
+#ifndef GNGF_RENDER_KERNELS_ONLY        // (render_score.hip takes the kernel and brings its own entry points)
 
 using RenderKern = void (*)(const RenderArgs, const RenderNoGrid);
 template <int KIN, typename TT> static RenderKern render_pick(bool leaky, bool exact, bool vt) {
@@ -370,8 +432,11 @@ template <int KIN> static RenderGridKern render_pick_grid(bool leaky, bool exact
   return exact ? render_kernel<KIN, false, true, kSrcGrid, float> : render_kernel<KIN, false, false, kSrcGrid, float>;
 }
 
+#endif  // GNGF_RENDER_KERNELS_ONLY
+
 }  // namespace gngf
 
+#ifndef GNGF_RENDER_KERNELS_ONLY
 // rgb (rows cols, out_dim) fp32 and / or img (same shape) int32 = (int)(rgb * 255.0f) of the model on the lattice
 // ((r0 + r) / denom, (c0 + c) / denom), r < rows, c < cols, row-major.  See include/gngf.h.
 extern "C" int gngf_render(const void* tables, int feat_dtype, const int32_t* vert_idx, const float* vert_w, const int32_t* n_ls,
@@ -446,3 +511,4 @@ extern "C" int gngf_render_grid(const float* grid, const int32_t* n_ls, const in
   fn<<<dim3(nwg), dim3(kDecThreads), smem, as_stream(stream)>>>(a, ga);
   GNGF_RETURN_LAUNCH();
 }
+#endif  // GNGF_RENDER_KERNELS_ONLY

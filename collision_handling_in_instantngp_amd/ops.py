@@ -2117,6 +2117,54 @@ def render_lattice(tables, n_ls, decoder_params, rows, cols, denom, origin=(0, 0
          float(denom), L, F, T, K, index_source(vert_idx, mode), int(vstride), NV, C, int(bool(leaky)), stream_ptr())
 
 
+def render_score_workspace(device):
+    """the per-workgroup partial sums of render_score (needs no clearing)"""
+    return torch.empty((query("gngf_ext2_render_score_workspace_words"),), dtype=_i64, device=device)
+
+
+def render_score(tables, n_ls, decoder_params, image, *, denom, step=1, sums, workspace, vert_idx=None, vert_w=None, vstride=0,
+                 leaky=False, mode=None):
+    """sums (2,) int64 = (#equal elements, sum of squared differences) of the model's image — the integers gngf_render stores,
+    (rgb * 255).int() — against the uint8 `image` (h,w,C) at the pixels (i step, j step), exact; no picture is written
+    (csrc/render.inc: the scoring form; include/gngf_ext2.h has the contract to the bit).  The model arguments are
+    render_lattice's.  workspace: render_score_workspace(device).  Everything is checked here, before any device work; no
+    allocation, no synchronisation: capturable.  Returns sums."""
+    L, T, F = tables.shape
+    W0, b0, W1, b1, W2, b2 = decoder_params
+    C = W2.shape[0]
+    if tuple(W0.shape) != (64, L * F) or tuple(W1.shape) != (64, 64) or W2.shape[1] != 64:
+        raise ValueError(f"render_score: decoder ({L * F} -> 64 -> 64 -> C) expected, got {tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
+    if n_ls.numel() != L:
+        raise ValueError(f"n_ls holds {n_ls.numel()} resolutions for {L} levels")
+    if image.dim() != 3:
+        raise ValueError(f"image must be (h, w, C), got {tuple(image.shape)}")
+    h, w, Ci = (int(s) for s in image.shape)
+    if Ci != C:
+        raise ValueError(f"image has {Ci} channel(s), the model {C}")
+    if not (1 <= h <= SAMPLE_MAX_SIDE and 1 <= w <= SAMPLE_MAX_SIDE):
+        raise ValueError(f"image sides must lie in [1, 2^24], got {h} x {w}")
+    step = int(step)
+    if step < 1:
+        raise ValueError(f"step must be >= 1, got {step}")
+    denom = float(denom)
+    if not denom > 0:
+        raise ValueError(f"denom must be > 0, got {denom}")
+    if sums.numel() != 2 or workspace.numel() < query("gngf_ext2_render_score_workspace_words"):
+        raise ValueError("sums must hold 2 words and workspace gngf_ext2_render_score_workspace_words() words")
+    vt = vert_idx is not None
+    K = check_topk(vert_idx.shape[1]) if vt else 0
+    tp, code = _tab(tables)
+    NV = int(vert_idx.shape[0]) if vt else 0
+    if vt and tuple(vert_w.shape) != (NV, K):
+        raise ValueError(f"vert_w must be (NV, K) = ({NV}, {K}), got {tuple(vert_w.shape)}")
+    call("gngf_ext2_render_score", tp, code, ptr(vert_idx, _i32, "vert_idx"), ptr(vert_w, _f32, "vert_w"), ptr(n_ls, _i32, "n_ls"),
+         ptr(W0, _f32, "W0"), ptr(b0, _f32, "b0"), ptr(W1, _f32, "W1"), ptr(b1, _f32, "b1"), ptr(W2, _f32, "W2"), ptr(b2, _f32, "b2"),
+         L, F, T, K, index_source(vert_idx, mode), int(vstride), NV, C, int(bool(leaky)),
+         ptr(image, torch.uint8, "image"), h, w, C, denom, min(step, 1 << 62), ptr(sums, _i64, "sums"),
+         ptr(workspace, _i64, "workspace"), stream_ptr())
+    return sums
+
+
 def _grid_vertices(n_ls_host):
     return sum((int(n) + 2) ** 2 for n in n_ls_host)
 

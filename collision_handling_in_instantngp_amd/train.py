@@ -831,8 +831,8 @@ def train_sampled(net, loss_fn, optimizer, sampler, steps, *, l_mse, l_js_kl, l_
     named to it, so a replayed step (graph=True: GraphedStep with the sampler's coord_bounds and cross_replay, cached on the net)
     bins its successor's pixels and none but the first bins at its head; an eager step (graph=False) is train_epoch's.  The call
     advances sampler.draw by steps + 1: the batch drawn ahead of the last step is not trained on (the next call draws its own).
-    Returns {"loss": (steps,), "mse": (steps,)} fp32 device tensors; nothing is read back to the host.  Scoring stays with
-    render_psnr(net, og_image).  Hash, dense_levels and GNGF models (frozen or trainable HPD); not should_batchnorm_data (the
+    Returns {"loss": (steps,), "mse": (steps,)} fp32 device tensors; nothing is read back to the host.  Scoring: score(net,
+    sampler) on the device (fit_sampled builds the epoch loop on both).  Hash, dense_levels and GNGF models (frozen or trainable HPD); not should_batchnorm_data (the
     sampler's coordinates are the unit square's) and not with a data-parallel exchange (the ranks would draw the same batches)."""
     steps = int(steps)
     if steps < 0:
@@ -1505,6 +1505,215 @@ def render_psnr(net, og_image):
     .accuracy() form them (integer sums on the device — gngf_image_metrics — floats on the host).  After fit():
     `res.best.restore(); image, psnr, acc = render_psnr(net, og_image)` is the best model's picture and score."""
     return _score_render(lambda h, w: render(net, h, w, rgb=False, image=True), net.mlp[-1][0].weight.shape[0], og_image)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Scoring: the model against the uint8 image it is trained on, in one render launch that writes no picture (csrc/render.inc:
+# the scoring form; include/gngf_ext2.h), and the epoch loop of fit() on batches a data.ImageSampler draws.
+
+def scored_elements(h, w, C, step=1):
+    """n of score(): the elements of the pixels (i step, j step) of an (h,w,C) image — ceil(h / step) ceil(w / step) C"""
+    h, w, C, step = int(h), int(w), int(C), int(step)
+    if h < 1 or w < 1 or C < 1 or step < 1:
+        raise ValueError(f"scored_elements: h, w, C and step are at least 1, got {(h, w, C, step)}")
+    return (-(-h // step)) * (-(-w // step)) * C
+
+
+def sse_order_refusal(n, who="fit_sampled()"):
+    """None, or the text of the refusal when n scored elements are too many for the integer save rule (n * 255^2 must not exceed
+    SSE_ORDER_LIMIT: DESIGN.md §3) — with the remedy a scored loop has, a coarser lattice"""
+    if int(n) * 255 ** 2 <= SSE_ORDER_LIMIT:
+        return None
+    return (f"{who}: {int(n)} scored elements — the integer save rule is shown to equal the reference's float PSNR comparison for "
+            f"n * 255^2 <= 2^44 only (DESIGN.md §3); score a coarser lattice: raise step (score_step)")
+
+
+def psnr_accuracy_from_sums(eq, sse, n, image_max):
+    """(psnr, accuracy) of score()'s two sums over n elements, as EpochImage forms them: psnr_from_sums with the peak term
+    20 * np.log10(np.max(image)) of the WHOLE uint8 image (numpy evaluates it in float16 for a uint8 maximum, and so does this),
+    accuracy = eq / n * 100."""
+    peak_term = 20 * np.log10(np.uint8(image_max))
+    return float(psnr_from_sums(int(sse), int(n), peak_term)), float((int(eq) / int(n)) * 100)
+
+
+def _score_image(image, denom):
+    """(uint8 device tensor (h,w,C), denom) of what score() was handed: a data.ImageSampler (its image and denom) or a tensor"""
+    from .data import ImageSampler
+    if isinstance(image, ImageSampler):
+        return image.image, (image.denom if denom is None else denom)
+    if not torch.is_tensor(image) or image.dtype != torch.uint8 or not image.is_cuda or not image.is_contiguous():
+        raise ValueError("score(): image must be a contiguous device uint8 tensor (h,w) / (h,w,C) or a data.ImageSampler")
+    if image.dim() == 2:
+        image = image.unsqueeze(-1)
+    if image.dim() != 3 or image.numel() == 0:
+        raise ValueError(f"score(): image must be (h,w) or (h,w,C), got {tuple(image.shape)}")
+    if denom is None:
+        denom = max(int(image.shape[0]), int(image.shape[1])) - 1
+        if denom < 1:
+            raise ValueError("score(): a 1 x 1 image has no default denom (max(h, w) - 1 = 0): pass denom")
+    return image, denom
+
+
+def _score_setup(net, image, step, denom, who):
+    """Validation shared by score() and fit_sampled(), render()'s: (image (h,w,C), denom, step) or ValueError naming net(x)."""
+    img, denom = _score_image(image, denom)
+    h, w, Ci = (int(s) for s in img.shape)
+    _check_lattice(h, w, denom, (0, 0))
+    step = int(step)
+    if step < 1:
+        raise ValueError(f"{who}: step must be >= 1, got {step}")
+    C = _check_render_model(net, who)
+    if Ci != C:
+        raise ValueError(f"{who}: the image has {Ci} channel(s), the model {C}" + _GENERAL_PATH)
+    if not net._hash_mode:
+        _check_unit_square(h, w, 0, 0, denom, f"{who}: GNGF indexing looks vertices up in the table")
+    elif getattr(net, "_dense_levels", False):
+        _check_unit_square(h, w, 0, 0, denom, f"{who}: a dense level clamps a vertex outside its grid, so the model is defined")
+    return img, float(np.float32(denom)), step
+
+
+@torch.no_grad()
+def score(net, image, *, step=1, denom=None, out=None):
+    """The model NOW against the image it is trained on: (2,) int64 on the device, [eq, sse] — the number of equal elements and
+    the sum of squared differences between (rgb * 255).int() of the model at the pixels (i step, j step) and the uint8 image
+    there, over n = scored_elements(h, w, C, step) elements.  One launch of the render kernel's scoring form and a one-workgroup
+    launch behind it: no int32 image, no upload, no synchronisation.  The integers are those of
+    ops.image_metrics(render(net, h, w, denom, image=True)[::step, ::step], image[::step, ::step]) — a scored pixel sees the
+    coordinate a full render gives it, and a pixel-centre training batch.
+    image: a device uint8 (h,w) / (h,w,C) tensor (denom None: max(h, w) - 1, render()'s default) or a data.ImageSampler (its image
+    and its denom); a 1 x 1 tensor image has no default and needs denom.  out: the (2,) int64 device tensor to write; with it, and the workspace cached on the net by an earlier
+    call, a hash-mode or frozen-HPD call allocates nothing and may be captured in a graph (a trainable HPD evaluates its vertex
+    table per call, as render() does).
+    ValueError: what render() refuses (should_batchnorm_data, a decoder other than [64, 64] with at most 4 outputs, L * F > 64,
+    F not in {1, 2, 4}, a GNGF or dense_levels model outside [0, 1]^2), a channel count other than the model's, step < 1 —
+    net(x) is the general path."""
+    img, denom, step = _score_setup(net, image, step, denom, "score()")
+    tables = net.encoding.packed_tables()
+    dev = tables.device
+    if out is None:
+        out = torch.empty((2,), dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or not out.is_cuda or not out.is_contiguous() or out.numel() != 2:
+        raise ValueError("score(): out must be a contiguous device int64 tensor of 2 elements")
+    ws = getattr(net, "_score_workspace", None)
+    if ws is None or ws.device != dev:
+        ws = net._score_workspace = ops.render_score_workspace(dev)
+    ti = w = None
+    vstride = 0
+    if not net._hash_mode:
+        ti, w, vstride = _render_vertex_table(net)
+    ops.render_score(tables, net._n_ls_flat(dev), [p.detach() for p in net._decoder_params()], img, denom=denom, step=step,
+                     sums=out, workspace=ws, vert_idx=ti, vert_w=w, vstride=vstride, leaky=net._leaky, mode=_index_source(net))
+    return out
+
+
+def score_psnr(net, image, *, step=1, denom=None):
+    """(psnr, accuracy) of the model against the image as host floats — score()'s sums read back (the one synchronisation),
+    formed by psnr_from_sums exactly as EpochImage forms them (psnr_accuracy_from_sums): the peak term comes from the WHOLE
+    image's maximum, n = scored_elements(h, w, C, step).  denom: score()'s (a 1 x 1 tensor image needs one)."""
+    img, denom = _score_image(image, denom)
+    eq, sse = score(net, image, step=step, denom=denom).cpu().numpy()
+    h, w, C = (int(s) for s in img.shape)
+    return psnr_accuracy_from_sums(eq, sse, scored_elements(h, w, C, step), int(img.max()))
+
+
+def _capture_guarded(body):
+    """(graph, body()) with body's launches captured into a torch.cuda.CUDAGraph.  NOT a second policy: this repeats, line for
+    line, the guard of GraphedStep._capture — no garbage collection while the stream captures (a finaliser that touches the
+    runtime during a capture aborts the process), capture_error_mode thread_local — for a body that is not a training step
+    (a captured score()).  Whoever changes one changes the other; folding _capture onto this helper is left to a change that
+    may touch the training step.  Warm body up eagerly first: what it allocates must exist before the capture."""
+    import gc
+    g = torch.cuda.CUDAGraph()
+    gc_was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            result = body()
+    finally:
+        if gc_was_on:
+            gc.enable()
+    return g, result
+
+
+def fit_sampled(net, loss_fn, optimizer, sampler, *, rounds, steps_per_round, tolerance, min_delta, should_reset=True, l_mse,
+                l_js_kl, l_collisions, score_step=1, graph=True, poll_every=16, exact_final=True, after_round=None):
+    """fit() for batches a data.ImageSampler draws: a round is steps_per_round steps of train_sampled, then score(net, sampler,
+    step=score_step), then one launch of gngf_epoch_tail — handed the round's per-step loss / mse and the score's sums, with
+    kls = colls = used = None — and the predicated copies into the `best` (and, exact_final, the `final`) snapshot: what fit()
+    does per epoch, with every decision on the device.  The host only enqueues; every poll_every rounds it reads one word.
+    The log's "epochs" are rounds; kls / colls_loss are NaN and used is empty.  The zero-collision stop is OFF: sampled training
+    tracks no indices, so there are no distinct-slot counts to check (stop_reason is 'epochs' or 'early_stopping').
+    after_round(r, rec): called once the launches of round r are enqueued, with train_sampled's {"loss", "mse"} of the round;
+    it must not synchronise if the loop is to stay free of host waits.
+    ValueError: what train_sampled refuses (should_batchnorm_data, a data-parallel exchange, a sampler with fewer than 2
+    buffers) and fit() refuses (an optimizer whose state lives on the host, rounds < 1), steps_per_round < 1, a model the render
+    kernel does not hold (score()'s refusals), and n * 255^2 > SSE_ORDER_LIMIT for the n = scored_elements(h, w, C, score_step)
+    scored elements — raise score_step."""
+    dp = getattr(net, "dp", None)
+    if dp is not None and (dp.exchange is not None or dp.active or dp.defer_vertex or dp.world > 1 or dp.zero is not None):
+        raise ValueError("fit_sampled() runs in one process: this model's data-parallel exchange is enabled")
+    if models.should_batchnorm_data:
+        raise ValueError("fit_sampled(): should_batchnorm_data moves the coordinates out of the unit square the sampler draws in")
+    if sampler.buffers < 2:
+        raise ValueError("fit_sampled(): train_sampled draws batch k + 1 while batch k is in use: the sampler needs buffers >= 2")
+    _refuse_host_state(optimizer)
+    rounds, steps_per_round, poll_every = int(rounds), int(steps_per_round), max(1, int(poll_every))
+    if rounds < 1 or steps_per_round < 1:
+        raise ValueError("fit_sampled(): rounds and steps_per_round must be at least 1")
+    img, _denom, score_step = _score_setup(net, sampler, score_step, None, "fit_sampled()")
+    n_elems = scored_elements(img.shape[0], img.shape[1], img.shape[2], score_step)
+    refusal = sse_order_refusal(n_elems)
+    if refusal is not None:
+        raise ValueError(refusal)
+    dev = img.device
+    peak_term = 20 * np.log10(np.uint8(int(img.max())))          # (one read, before the loop)
+    L = net._num_levels
+    nverts = torch.from_numpy(np.asarray(net._level_vertex_counts(), dtype=np.int64)).to(dev)
+    state = torch.from_numpy(new_epoch_state(sse_limit0(n_elems, peak_term)).reshape(1).view(np.uint8).copy()).to(dev)
+    flags = state.view(torch.int32)
+    take, last, finished = flags[0:1], flags[1:2], flags[2:3]
+    polled = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
+    sums = torch.zeros((2,), dtype=torch.int64, device=dev)
+    logf = torch.full((rounds, 2 + 2 * L), float("nan"), dtype=torch.float64, device=dev)
+    logi = torch.zeros((rounds, 6), dtype=torch.int64, device=dev)
+    best = final = None
+    issued = 0
+    for r in range(rounds):
+        rec = train_sampled(net, loss_fn, optimizer, sampler, steps_per_round, l_mse=l_mse, l_js_kl=l_js_kl,
+                            l_collisions=l_collisions, graph=graph)
+        if best is None:
+            # the optimizer's state exists now (the first step has run): the shadows are allocated once, here
+            tensors = state_tensors(net, optimizer)
+            best = DeviceSnapshot(tensors)
+            final = DeviceSnapshot(tensors) if exact_final else None
+        score(net, sampler, step=score_step, out=sums)
+        ops.epoch_tail(state, logf, logi, rec["loss"], rec["mse"], None, None, sums, None, nverts, hash_source=net._hash_mode,
+                       tolerance=tolerance, min_delta=min_delta, should_reset=should_reset, epochs=rounds)
+        best.take_if(take)
+        if final is not None:
+            final.take_if(last)
+        issued = r + 1
+        if after_round is not None:
+            after_round(r, rec)
+        if issued % poll_every == 0 or issued == rounds:
+            polled.copy_(finished, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            if int(polled[0]) != 0:
+                break
+    st = state.cpu().numpy().view(EPOCH_STATE)[0]
+    last_epoch, best_epoch = int(st["last_epoch"]), int(st["best_epoch"])
+    restored = False
+    if issued > last_epoch + 1 and final is not None:
+        final.restore()
+        restored = True
+    n = last_epoch + 1
+    lf, li = logf[:n].cpu().numpy(), logi[:n].cpu().numpy()
+    log = {"loss": lf[:, 0], "mse": lf[:, 1], "kls": lf[:, 2:2 + L], "colls_loss": lf[:, 2 + L:2 + 2 * L], "eq": li[:, 0],
+           "sse": li[:, 1], "counter": li[:, 2], "saved": li[:, 3].astype(bool), "stopper_fired": li[:, 4].astype(bool),
+           "zero_stop": li[:, 5].astype(bool), "used": li[:, 6:].reshape(n, 0, L)}
+    log["psnr"] = np.array([float(psnr_from_sums(s, n_elems, peak_term)) for s in log["sse"]], dtype=np.float64)
+    log["accuracy"] = np.array([float((q / n_elems) * 100) for q in log["eq"]], dtype=np.float64)
+    return FitResult(log, last_epoch, best_epoch, STOP_REASONS[int(st["reason"])], best, issued, restored)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
