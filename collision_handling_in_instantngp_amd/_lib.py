@@ -116,8 +116,8 @@ EXT_SIGNATURES = {
 
 EXT_VERSION = 1
 
-# include/gngf_ext.h is closed as well (two names, version 1).  include/gngf_ext2.h is the open one: a new entry point is added
-# there and here, and GNGF_EXT2_VERSION / EXT2_VERSION rise together.
+# include/gngf_ext.h is closed as well (two names, version 1).  include/gngf_ext2.h holds the scoring entry points (EXT3 below is
+# the table that grows).
 EXT2_SIGNATURES = {
     "gngf_ext2_version": [],
     "gngf_ext2_render_score_workspace_words": [],
@@ -126,6 +126,23 @@ EXT2_SIGNATURES = {
 }
 
 EXT2_VERSION = 1
+
+# include/gngf_ext2.h stays as it is too: the ledger of its guard-band cases lives in a test file.  include/gngf_ext3.h is the open
+# header: a new entry point is added there and here, GNGF_EXT3_VERSION / EXT3_VERSION rise together, and its guard-band cases are
+# found by their test module's ext3_entry_points() — or, where it writes no device memory, the reason stands in EXT3_WRITES_NOTHING.
+_QUERY_TAIL = [_P, _L, _P, _P, _P]          # xy, P, rgb, img, stream
+EXT3_SIGNATURES = {
+    "gngf_ext3_version": [],
+    "gngf_ext3_query": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _I, _L, _I, _I] + _QUERY_TAIL,
+    "gngf_ext3_query_grid": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I] + _QUERY_TAIL,
+}
+
+EXT3_VERSION = 1
+
+# entry points of include/gngf_ext3.h that take no writable pointer: name -> why no guard-band case is owed
+EXT3_WRITES_NOTHING = {
+    "gngf_ext3_version": "returns a constant",
+}
 
 
 class BinJob(ctypes.Structure):
@@ -152,7 +169,8 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C collision_handling_in_instantngp_amd/csrc`.  There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(EXT2_SIGNATURES.items()):
+    for name, argtypes in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(EXT2_SIGNATURES.items())
+                           + list(EXT3_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -168,6 +186,9 @@ def load():
     ext2 = lib.gngf_ext2_version()
     if ext2 != EXT2_VERSION:
         raise GngfLibraryError(f"extension version mismatch (include/gngf_ext2.h): library {ext2}, binding {EXT2_VERSION}")
+    ext3 = lib.gngf_ext3_version()
+    if ext3 != EXT3_VERSION:
+        raise GngfLibraryError(f"extension version mismatch (include/gngf_ext3.h): library {ext3}, binding {EXT3_VERSION}")
     _lib = lib
     return lib
 

@@ -26,6 +26,12 @@
 // operations, but the sink is a comparison — the integer (int32_t)(y * 255.0f) against the uint8 image the lattice was laid over
 // (pixel (i step, j step) of it), accumulated per lane as two exact int64 sums, reduced across the wave, through LDS across the
 // workgroup's waves, and stored as the workgroup's two partial sums.  Nothing of the picture is written.
+// Query forms (the kSrc*Query sources, instantiated in render_query.hip: gngf_ext3_query / gngf_ext3_query_grid): the same
+// values by the same operations at coordinates READ from xy (P, 2) fp32 — (row coordinate, column coordinate), one float2 load
+// a point — instead of formed from a row and a column.  A block is 128 consecutive points, point wave 32 + (lane & 31) of it for
+// both lane halves (neighbouring lanes load neighbouring float2s); the next block's coordinates are requested where the lattice
+// forms compute them, a block ahead and outside every divergent branch (a lane past P reads xy[P - 1]); the sink is row p of
+// rgb / img (P, out_dim).  The host hands the walk a one-block-high lattice of ceil(P / 128) blocks: block column = block.
 namespace gngf {
 
 constexpr int kRenderCols = 16, kRenderRows = 8;        // the workgroup's block; a wave renders 8 x 4 of it
@@ -37,6 +43,12 @@ constexpr int kSrcDenseHash = 3;
 // instead of storing.  A source of its own, not a further template parameter: the storing instantiations keep their names.
 constexpr int kSrcScore = 4;
 constexpr int kSrcHashScore = kSrcScore + kSrcHash, kSrcTableScore = kSrcScore + kSrcTable, kSrcDenseHashScore = kSrcScore + kSrcDenseHash;
+// The query forms: source kSrcQuery + s gathers as source s (all four) at coordinates read from memory.  Sources of their own for
+// the scoring forms' reason: the storing and scoring instantiations keep their names and their code.
+constexpr int kSrcQuery = 8;
+constexpr int kSrcHashQuery = kSrcQuery + kSrcHash, kSrcTableQuery = kSrcQuery + kSrcTable, kSrcGridQuery = kSrcQuery + kSrcGrid,
+              kSrcDenseHashQuery = kSrcQuery + kSrcDenseHash;
+constexpr int kQueryBlock = kRenderCols * kRenderRows;    // points of a query block: one per pixel of a lattice block
 
 struct RenderArgs {
   const void* tables; const int32_t* vert_idx; const float* vert_w; const int32_t* n_ls;
@@ -63,6 +75,13 @@ struct RenderScore { const uint8_t* image; int64_t w, step; int64_t* partial; };
 template <> struct RenderSrcArgs<kSrcHashScore> { using type = RenderScore; };
 template <> struct RenderSrcArgs<kSrcTableScore> { using type = RenderScore; };
 template <> struct RenderSrcArgs<kSrcDenseHashScore> { using type = RenderScore; };
+// the query forms' second argument: xy (P, 2) fp32, 8-byte aligned, P >= 1 — and, for the baked form, the grid source's own
+struct RenderQuery { const float* xy; int64_t P; };
+struct RenderQueryGrid { const float* xy; int64_t P; const float* grid; int64_t goff[GNGF_MAX_LEVELS]; };
+template <> struct RenderSrcArgs<kSrcHashQuery> { using type = RenderQuery; };
+template <> struct RenderSrcArgs<kSrcTableQuery> { using type = RenderQuery; };
+template <> struct RenderSrcArgs<kSrcDenseHashQuery> { using type = RenderQuery; };
+template <> struct RenderSrcArgs<kSrcGridQuery> { using type = RenderQueryGrid; };
 
 // one table row (F consecutive values, F sizeof(TT)-aligned: the table base is 16-byte aligned) as fp32 — tload's values
 template <int F> __device__ __forceinline__ void row_load(const float* r, float (&o)[F]) {
@@ -245,8 +264,9 @@ template <int KIN, bool LEAKY, bool EXACT, int SRC, typename TT>
 __global__ void __launch_bounds__(kDecThreads, 1)
 render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
   constexpr int S0 = KIN / 2, NG = S0 / 16;
-  constexpr bool SCORE = SRC >= kSrcScore;                 // ga is the RenderScore sink; a.rows x a.cols its lattice, a.r0 = a.c0 = 0
-  constexpr int GSRC = SCORE ? SRC - kSrcScore : SRC;      // where the corners come from
+  constexpr bool QUERY = SRC >= kSrcQuery;                 // ga holds xy and P; a.rows x a.cols = 8 x 16 ceil(P / 128): a row of blocks
+  constexpr bool SCORE = SRC >= kSrcScore && !QUERY;       // ga is the RenderScore sink; a.rows x a.cols its lattice, a.r0 = a.c0 = 0
+  constexpr int GSRC = QUERY ? SRC - kSrcQuery : SCORE ? SRC - kSrcScore : SRC;      // where the corners come from
   const int in_dim = EXACT ? KIN : a.L * a.F;
   const int out_dim = a.out_dim;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
@@ -289,8 +309,15 @@ render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
   const int lr = (wave >> 1) * 4 + (i >> 3), lc = (wave & 1) * 8 + (i & 7);      // this lane's pixel inside a block
   // (r0 + rows, c0 + cols <= 2^24: the integers are exact in fp32; lanes past the ragged edges store nothing — in the scoring
   // forms they compute the last row / column's pixel again and are masked out of the sums)
+  [[maybe_unused]] const int lp = wave * 32 + i;            // (query forms) this lane's point inside a block
   auto coord = [&](int64_t brow, int64_t bcol, float& x, float& y) {
-    if constexpr (SCORE) {
+    if constexpr (QUERY) {
+      // point bcol 128 + lp (brow is 0), one 8-byte load; a lane past the end takes the last point's coordinate — a valid
+      // address, no branch — and stores nothing
+      const int64_t p = bcol * kQueryBlock + lp;
+      const float2 q = reinterpret_cast<const float2*>(ga.xy)[p < ga.P ? p : ga.P - 1];          // 64-bit offsets
+      x = q.x; y = q.y;
+    } else if constexpr (SCORE) {
       // image pixel (r step, c step) of lattice point (r, c) — an exact integer < 2^24 — over denom; a lane past a ragged edge
       // takes the last row / column's coordinate (inside the image, as every gather of the model expects) and adds nothing
       const int64_t r = brow * kRenderRows + lr, c = bcol * kRenderCols + lc;
@@ -310,6 +337,7 @@ render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
     RENDER_F(render_issue<kF, GSRC, EXACT, TT>(G, a, ga, h * (S0 / kF) + 16 / kF, x, y); render_combine<kF, 16>(G, xr));
   for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
     const int64_t pr = by * kRenderRows + lr, pc = bx * kRenderCols + lc;         // this block's pixel
+    [[maybe_unused]] const int64_t pq = bx * kQueryBlock + lp;                    // (query forms) this block's point
     [[maybe_unused]] uint32_t tv[4] = {0u, 0u, 0u, 0u};      // scoring forms: the pixel's texels, requested ahead of the MFMA runs
     if constexpr (SCORE) {
       // no divergent branch: a lane past a ragged edge reads the last row / column's texel (a valid address) and is masked below
@@ -383,6 +411,16 @@ render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
             eq += mine && d == 0;
             sse += mine ? d * d : 0;
           }
+      } else if constexpr (QUERY) {
+        if (h == 0 && pq < ga.P) {
+          const int64_t e = pq * out_dim;
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (c < out_dim) {
+              if (a.rgb) a.rgb[e + c] = yv[c];
+              if (a.img) a.img[e + c] = (int32_t)(yv[c] * 255.0f);
+            }
+        }
       } else if (h == 0 && pr < a.rows && pc < a.cols) {
         const int64_t e = (pr * a.cols + pc) * out_dim;
 #pragma unroll

@@ -2222,6 +2222,81 @@ def render_grid(grid, n_ls, n_ls_host, decoder_params, rows, cols, denom, origin
          float(denom), L, F, C, int(bool(leaky)), stream_ptr())
 
 
+def check_query_xy(who, xy):
+    """P of xy, a contiguous 8-byte aligned device float32 (P, 2) tensor of (row, column) coordinates — or ValueError"""
+    if not isinstance(xy, torch.Tensor) or not xy.is_cuda or xy.dtype != _f32 or xy.dim() != 2 or xy.shape[1] != 2 \
+            or not xy.is_contiguous():
+        what = f"{xy.device} {xy.dtype} {tuple(xy.shape)}" if isinstance(xy, torch.Tensor) else type(xy).__name__
+        raise ValueError(f"{who}: xy must be a contiguous device float32 (P, 2) tensor of (row, column) coordinates, got {what}")
+    P = int(xy.shape[0])
+    if xy.data_ptr() % 8:
+        raise ValueError(f"{who}: xy must be 8-byte aligned (one load a point)")
+    return P
+
+
+def _query_tail(who, xy, C, out_rgb, out_image):
+    """P of a query after its checks: check_query_xy, at least one output, each of P * C elements"""
+    P = check_query_xy(who, xy)
+    if out_rgb is None and out_image is None:
+        raise ValueError(f"{who}: pass out_rgb, out_image or both")
+    for name, t, dt in (("out_rgb", out_rgb, _f32), ("out_image", out_image, _i32)):
+        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != P * C):
+            raise ValueError(f"{name} must be a contiguous device {dt} tensor of {P} x {C} elements")
+    return P
+
+
+def query_points(tables, n_ls, decoder_params, xy, *, vert_idx=None, vert_w=None, vstride=0, leaky=False, out_rgb=None,
+                 out_image=None, mode=None):
+    """The model at the coordinates xy (P, 2) fp32 — (row, column), a training batch's order — in one forward-only launch
+    (csrc/render.inc: the query forms; include/gngf_ext3.h has the contract to the bit): row p of out_rgb (P, C) fp32 and / or
+    out_image (P, C) int32 is what render_lattice writes for a lattice point with the same float32 coordinate.  The model
+    arguments are render_lattice's.  Everything is checked here, before any device work; no autograd, no workspace, no
+    allocation, no synchronisation: capturable.  P = 0 launches nothing."""
+    L, T, F = tables.shape
+    W0, b0, W1, b1, W2, b2 = decoder_params
+    C = W2.shape[0]
+    if tuple(W0.shape) != (64, L * F) or tuple(W1.shape) != (64, 64) or W2.shape[1] != 64:
+        raise ValueError(f"query_points: decoder ({L * F} -> 64 -> 64 -> C) expected, got {tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
+    if n_ls.numel() != L:
+        raise ValueError(f"n_ls holds {n_ls.numel()} resolutions for {L} levels")
+    P = _query_tail("query_points", xy, C, out_rgb, out_image)
+    vt = vert_idx is not None
+    K = check_topk(vert_idx.shape[1]) if vt else 0
+    tp, code = _tab(tables)
+    NV = int(vert_idx.shape[0]) if vt else 0
+    if vt and tuple(vert_w.shape) != (NV, K):
+        raise ValueError(f"vert_w must be (NV, K) = ({NV}, {K}), got {tuple(vert_w.shape)}")
+    if P == 0:
+        return
+    call("gngf_ext3_query", tp, code, ptr(vert_idx, _i32, "vert_idx"), ptr(vert_w, _f32, "vert_w"), ptr(n_ls, _i32, "n_ls"),
+         ptr(W0, _f32, "W0"), ptr(b0, _f32, "b0"), ptr(W1, _f32, "W1"), ptr(b1, _f32, "b1"), ptr(W2, _f32, "W2"), ptr(b2, _f32, "b2"),
+         L, F, T, K, index_source(vert_idx, mode), int(vstride), NV, C, int(bool(leaky)),
+         ptr(xy, _f32, "xy"), P, ptr(out_rgb, _f32, "out_rgb"), ptr(out_image, _i32, "out_image"), stream_ptr())
+
+
+def query_grid_points(grid, n_ls, n_ls_host, decoder_params, xy, *, leaky=False, out_rgb=None, out_image=None):
+    """query_points from a baked vertex grid (render_grid's model arguments; gngf_ext3_query_grid).  Corners are clamped to the
+    level's grid, so no coordinate faults; only coordinates in [0, 1]^2 give the model's values."""
+    L = len(n_ls_host)
+    W0, b0, W1, b1, W2, b2 = decoder_params
+    C = W2.shape[0]
+    vtot = _grid_vertices(n_ls_host)
+    if grid.dim() != 2 or grid.shape[0] != vtot:
+        raise ValueError(f"query_grid_points: grid must be ({vtot}, F) for these resolutions, got {tuple(grid.shape)}")
+    F = int(grid.shape[1])
+    if tuple(W0.shape) != (64, L * F) or tuple(W1.shape) != (64, 64) or W2.shape[1] != 64:
+        raise ValueError(f"query_grid_points: decoder ({L * F} -> 64 -> 64 -> C) expected, got {tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
+    if n_ls.numel() != L:
+        raise ValueError(f"n_ls holds {n_ls.numel()} resolutions for {L} levels")
+    P = _query_tail("query_grid_points", xy, C, out_rgb, out_image)
+    if P == 0:
+        return
+    call("gngf_ext3_query_grid", ptr(grid, _f32, "grid"), ptr(n_ls, _i32, "n_ls"), (_ct.c_int32 * L)(*[int(n) for n in n_ls_host]),
+         ptr(W0, _f32, "W0"), ptr(b0, _f32, "b0"), ptr(W1, _f32, "W1"), ptr(b1, _f32, "b1"), ptr(W2, _f32, "W2"), ptr(b2, _f32, "b2"),
+         L, F, C, int(bool(leaky)), ptr(xy, _f32, "xy"), P, ptr(out_rgb, _f32, "out_rgb"), ptr(out_image, _i32, "out_image"),
+         stream_ptr())
+
+
 # Keep the decoder's activated hidden layers (512 B / pixel) from forward to backward instead of recomputing them: the
 # stores and loads ride under the MFMAs of kernels that leave most of the HBM bandwidth unused (decoder backward 345 -> ~230 us
 # at 2^20 px).  False: recompute (no extra memory).

@@ -1478,6 +1478,73 @@ def render(net, rows, cols, denom=None, origin=(0, 0), *, rgb=True, image=False,
     return out_rgb if out_rgb is not None else out_image
 
 
+def _query_outputs(P, C, dev, rgb, image, out_rgb, out_image, who):
+    """_render_outputs for P points: rgb (P, C) float32, image (P, C) int32 — (P,) for one channel"""
+    rgb, image = bool(rgb) or out_rgb is not None, bool(image) or out_image is not None
+    if not (rgb or image):
+        raise ValueError(f"{who}: ask for rgb, image or both")
+    for name, t, dt in (("out_rgb", out_rgb, torch.float32), ("out_image", out_image, torch.int32)):
+        if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() != P * C):
+            raise ValueError(f"{name} must be a contiguous device {dt} tensor of {P} x {C} elements")
+    if rgb and out_rgb is None:
+        out_rgb = torch.empty((P, C), dtype=torch.float32, device=dev)
+    if image and out_image is None:
+        out_image = torch.empty((P, C) if C != 1 else (P,), dtype=torch.int32, device=dev)
+    return out_rgb, out_image
+
+
+def _check_query_coordinates(xy, who, unit_square_why):
+    """check=True of query(): one min / max reduction, one host read.  ValueError for a non-finite coordinate; with
+    unit_square_why (the sources that clamp a vertex), for a coordinate outside [0, 1]^2, worded as render()'s refusal."""
+    if xy.numel() == 0:
+        return
+    lo, hi = (float(v) for v in torch.stack(torch.aminmax(xy)).tolist())        # (NaN propagates through both)
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"{who}: xy holds non-finite coordinates (min {lo:g}, max {hi:g})")
+    if unit_square_why is not None and (lo < 0 or hi > 1):
+        raise ValueError(f"{unit_square_why} over [0, 1]^2; these coordinates span [{lo:g}, {hi:g}]" + _GENERAL_PATH)
+
+
+@torch.no_grad()
+def query(net, xy, *, rgb=True, image=False, out_rgb=None, out_image=None, check=True):
+    """The model as it is NOW at the coordinates xy — a contiguous device float32 (P, 2) tensor of (row, column) coordinates, the
+    order of a training batch (a sampler's x is a valid xy) and of lattice_coordinates — in one launch of gngf_ext3_query: no
+    binning, no (P, L F) encoding in memory, none of the reference-shaped index / probability outputs.  Row p is, bit for bit,
+    what render() gives a lattice point with the same float32 coordinate.
+    Returns what was asked for, as render() does: rgb (P, C) float32, image (P, C) int32 — (P,) for a should_bw model —
+    = (rgb * 255).int(), or the pair.  out_rgb / out_image: buffers to write instead of new tensors (each implies its output).
+    check=True: one min / max reduction of xy and one host read — ValueError for non-finite coordinates, and for coordinates
+    outside [0, 1]^2 where the index source clamps a vertex (GNGF indexing, dense levels): the value there is not the model's.
+    Hash indexing is defined on the whole plane.  check=False reads nothing back: with every requested output given, a
+    hash-mode or frozen-HPD call allocates nothing and never synchronises, so it may be captured in a graph; out-of-range
+    coordinates then read a clamped vertex (never outside a buffer), non-finite ones give unspecified values.
+    ValueError for what render() refuses — should_batchnorm_data, a decoder other than [64, 64] with at most 4 outputs,
+    L * F > 64, F not in {1, 2, 4}: net(x) is the general path — and for an xy of another kind."""
+    C = _check_render_model(net, "query()")
+    P = ops.check_query_xy("query()", xy)
+    out_rgb, out_image = _query_outputs(P, C, xy.device, rgb, image, out_rgb, out_image, "query()")
+    if check:
+        why = None
+        if not net._hash_mode:
+            why = "query(): GNGF indexing looks vertices up in the table"
+        elif getattr(net, "_dense_levels", False):
+            why = "query(): a dense level clamps a vertex outside its grid, so the model is defined"
+        _check_query_coordinates(xy, "query()", why)
+    tables = net.encoding.packed_tables()
+    if tables.device != xy.device:
+        raise ValueError(f"query(): xy is on {xy.device}, the model on {tables.device}")
+    ti = w = None
+    vstride = 0
+    if not net._hash_mode:
+        ti, w, vstride = _render_vertex_table(net)
+    ops.query_points(tables, net._n_ls_flat(tables.device), [p.detach() for p in net._decoder_params()], xy,
+                     vert_idx=ti, vert_w=w, vstride=vstride, leaky=net._leaky, out_rgb=out_rgb, out_image=out_image,
+                     mode=_index_source(net))
+    if out_rgb is not None and out_image is not None:
+        return out_rgb, out_image
+    return out_rgb if out_rgb is not None else out_image
+
+
 def _score_render(render_image, out_dim, og_image):
     """render_psnr of the model and of a BakedGrid: render_image(h, w) -> int32 device image, scored against og_image."""
     og = np.asarray(og_image)
@@ -1773,6 +1840,24 @@ class BakedGrid:
                                              "BakedGrid.render()")
         ops.render_grid(self.grid, self.n_ls, self.n_ls_host, self.decoder, rows, cols, float(np.float32(denom)), (r0, c0),
                         leaky=self.leaky, out_rgb=out_rgb, out_image=out_image)
+        if out_rgb is not None and out_image is not None:
+            return out_rgb, out_image
+        return out_rgb if out_rgb is not None else out_image
+
+    @torch.no_grad()
+    def query(self, xy, *, rgb=True, image=False, out_rgb=None, out_image=None, check=True):
+        """train.query's contract, return shapes and validation, from the baked grid: one launch of gngf_ext3_query_grid, row p
+        bit for bit what render() gives a lattice point with the same float32 coordinate.  check=True refuses non-finite
+        coordinates and coordinates outside [0, 1]^2 whatever the model's index source was — a baked hash model has no rows
+        beyond its grids; check=False reads nothing back (capturable with the outputs given) and clamps."""
+        P = ops.check_query_xy("BakedGrid.query()", xy)
+        if xy.device != self.grid.device:
+            raise ValueError(f"BakedGrid.query(): xy is on {xy.device}, the grid on {self.grid.device}")
+        out_rgb, out_image = _query_outputs(P, self.out_dim, xy.device, rgb, image, out_rgb, out_image, "BakedGrid.query()")
+        if check:
+            _check_query_coordinates(xy, "BakedGrid.query()", "BakedGrid.query(): a baked model holds the vertices of its levels")
+        ops.query_grid_points(self.grid, self.n_ls, self.n_ls_host, self.decoder, xy, leaky=self.leaky, out_rgb=out_rgb,
+                              out_image=out_image)
         if out_rgb is not None and out_image is not None:
             return out_rgb, out_image
         return out_rgb if out_rgb is not None else out_image
