@@ -135,9 +135,15 @@ __device__ unsigned long long g_bwd_span[2];
 __device__ unsigned long long g_stamps[16];
 __device__ unsigned long long g_fstamps[16];
 __device__ unsigned long long g_blocktime[2][256][2];   // [fwd/bwd][workgroup][start, end] (s_memtime)
-#define STAMP(k) do { unsigned long long t_; __builtin_amdgcn_sched_barrier(0); \
+// -DGNGF_STAMP_MASK=<bits>: only the stamps whose bit is set are compiled in (the others are nothing, not even a scheduling
+// barrier); a stamp then holds the cycles since the previous SELECTED stamp in program order.  The training kernel stands at
+// 512 registers: with all 16 stamps it spills, with three or four it does not (tools/perf_decoder_train.py --stamps).
+#ifndef GNGF_STAMP_MASK
+#define GNGF_STAMP_MASK 0xffff
+#endif
+#define STAMP(k) do { if constexpr ((((GNGF_STAMP_MASK) >> (k)) & 1) != 0) { unsigned long long t_; __builtin_amdgcn_sched_barrier(0); \
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); __builtin_amdgcn_sched_barrier(0); \
-    ph[k] += t_ - tlast; tlast = t_; } while (0)
+    ph[k] += t_ - tlast; tlast = t_; } } while (0)
 #else
 #define STAMP(k) do {} while (0)
 #endif
@@ -478,6 +484,7 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
   constexpr int kImgZ = 2 * kImgFloats * 4;
   constexpr int kImgX = BL::kDedicatedX ? (2 * kImgFloats + 4 * kImgStride) * 4 : kImgB;
   const unsigned wDz3 = aImg + (unsigned)i * 4u;                                // dz3 -> rows c of imgZ
+  const unsigned wDz3h = aImg + (unsigned)(h * kImgStride + i) * 4u;            // TRAIN: the lane half's rows h, 2 + h of imgZ
   const unsigned wX = aImg + (unsigned)(h * S0 * kImgStride + i) * 4u;          // x slice -> rows h*S0 + s of imgX
   const unsigned rOp = aImg + (unsigned)(i * kImgStride + 16 * h) * 4u;         // operand rows i (+32), pixels 16h + 2q, 2q+1
   const unsigned rZ2 = aImg + (unsigned)((lane & 3) * kImgStride) * 4u;         // dW2: A rows lane & 3 of imgZ, all 32 pixels
@@ -485,7 +492,7 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
   f32x16 dW1acc[2][2], dW0acc[2][TX];
   f32x4 dW2acc = {0.f, 0.f, 0.f, 0.f};                   // lane j: dW2[c][j], c = 0..3
   float db0acc[2] = {0.f, 0.f}, db1acc[2] = {0.f, 0.f};  // lane (i,h): partial of db[32a + i] over the half's 16 pixels
-  float db2acc[4] = {0.f, 0.f, 0.f, 0.f};                // both lane halves accumulate the same pixel; half 0 is used
+  float db2acc[4] = {0.f, 0.f, 0.f, 0.f};                // both lane halves accumulate the same pixel; half 0 is used (TRAIN: see yoffh)
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
 #pragma unroll
@@ -529,10 +536,13 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
   // the batch read zeros (so dz3 = 0 and they contribute nothing anywhere) and their stores are dropped — no masks.
   const unsigned xoff = (unsigned)(((wave * 32 + i) * in_dim + (EXACT ? h * S0 : 0)) * 4);
   const unsigned yoff = (unsigned)(((wave * 32 + i) * out_dim) * 4);
+  // TRAIN: from the output layer's cross-half sum on, lane half h carries channels h and 2 + h of its pixel (slot sk = channel
+  // 2 sk + h of yn / dyn / dz3 / db2acc / b2v): the half's target loads, rgb stores and dz3 image rows go through these offsets
+  const unsigned yoffh[2] = {h < out_dim ? yoff + 4u * h : 0x40000000u, 2 + h < out_dim ? yoff + 4u * (2 + h) : 0x40000000u};
   // Pipeline: x of tile t+1 is loaded straight into xr as soon as tile t has consumed it (after layer 1 / after the x
   // image is written), y and dy of tile t+1 once dz3 of tile t is dead; both land long before the next tile starts, and
   // the d-enc stores at the end of a tile are issued after them, so no wait ever covers a store (vmcnt counts in order).
-  float xr[S0], yn[4], dyn[4], dz3[4];
+  float xr[S0], yn[4], dyn[4], dz3[4];                    // (TRAIN: slots 0, 1 only — the lane half's channels h, 2 + h)
   // fused pixel loss (torch.nn.MSELoss backward, csrc/loss.hip::mse_bwd_kernel): d rgb = gloss * 2/n * (rgb - target) is formed
   // here from the target instead of being read from a tensor a separate kernel wrote — the same expression, the same bits
   const bool fused_loss = target != nullptr;              // wave-uniform
@@ -567,16 +577,21 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
     tile_window(t, tt, rows);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Yout) + tt * 128 * out_dim, 0, rows * out_dim * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dsrc) + tt * 128 * out_dim, 0, rows * out_dim * 4, 0x00020000);
+    if constexpr (TRAIN) {                                // the lane half's own two channels (see the output layer)
+#pragma unroll
+      for (int sk = 0; sk < 2; ++sk) dyn[sk] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, yoffh[sk], 0, 0));
+    } else {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const unsigned off = c < out_dim ? yoff + 4u * c : 0x40000000u;
-      if constexpr (!TRAIN) yn[c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, off, 0, 0));
+      yn[c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, off, 0, 0));
       dyn[c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, off, 0, 0));
+    }
     }
   };
   auto make_dz3 = [&]() {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
+    for (int c = 0; c < (TRAIN ? 2 : 4); ++c) {
       const float dy = fused_loss ? kloss * (yn[c] - dyn[c]) : dyn[c];
       dz3[c] = dy * (yn[c] * (1.f - yn[c]));              // Sigmoid backward; 0 for padding pixels and channels
       asm volatile("" : "+v"(dz3[c]));                   // (keeps dz3 in registers: it is selected by lane half below)
@@ -589,7 +604,7 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
   float b2v[4] = {0.f, 0.f, 0.f, 0.f};
   if constexpr (TRAIN) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) b2v[c] = raw[ro.b2 + c];
+    for (int sk = 0; sk < 2; ++sk) b2v[sk] = raw[ro.b2 + 2 * sk + h];
   }
   // biases: accumulator-file residents, the C operand of the first MFMA of each recompute chain
   f32x16 b0v[2], b1v[2];
@@ -688,6 +703,7 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
     pin_acc();
     STAMP(0);
     float f1[2][32];
+    float a2t[2][2];
     if constexpr (TRAIN) {
       // ---- forward of the tile on the bf16 pipe (exact three-way split): h1 = act(W0 x + b0), h2 = act(W1 h1 + b1).
       // Software pipeline: the planes of the next k-chunk are requested and the next chunk's operand is split while the
@@ -798,6 +814,8 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
 #pragma unroll
       for (int g = 0; g < 8; ++g) w2v[g] = *reinterpret_cast<const f32x4*>(w2L + (g * 64 + lane) * 4);
 #pragma unroll
+      for (int sk = 0; sk < 2; ++sk) { a2t[0][sk] = A2T[(0 * 2 + sk) * 64 + lane]; a2t[1][sk] = A2T[(1 * 2 + sk) * 64 + lane]; }      // dh2's W2^T fragments
+#pragma unroll
       for (int r = 0; r < 16; ++r) acc2[1][r] = hidden_act<LEAKY>(acc2[1][r]);      // (tile 0's went under tile 1's last products)
       STEP_END();                                          // (the 4x4 MFMAs below must not follow their operand's v_max directly)
       STAMP(11);
@@ -815,16 +833,39 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
         int64_t rem = (P - tile * 128) * out_dim * 4;
         rem = rem > 128 * out_dim * 4 ? 128 * out_dim * 4 : rem;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Yout) + tile * 128 * out_dim, 0, (int)rem, 0x00020000);
+        // Cross-half sum without LDS: v_permlane32_swap exchanges the upper 32 lanes of its first operand with the lower 32 of
+        // its second, so after one swap of (channel 2 sk, channel 2 sk + 1) the two results hold, in lane half h, the half's own
+        // and its partner's partial of channel 2 sk + h — one add is that channel's sum (own + partner in half 0, partner + own in
+        // half 1: the same two values, the same bits as dc + __shfl_xor(dc, 32)).  A swap moves 32 values each way, so two swaps
+        // cannot hand all four sums to both halves: each half goes on with its two channels — bias, sigmoid, rgb store, d rgb,
+        // dz3 — which are exactly the two dh2 selects per half below (bsel), and every value is formed by the operations that
+        // formed it before.  The transcendentals issue as groups (two v_exp, two adds, two v_rcp), the stores behind them.
+        float z[2], e[2], y[2];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float dc = o0[c] + o1[c];
-          const float z = dc + __shfl_xor(dc, 32, 64) + b2v[c];
-          const float y = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z * -1.4426950408889634f));
-          const unsigned off = (h == 0 && c < out_dim) ? yoff + 4u * c : 0x40000000u;
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y), rs, off, 0, 0);
-          // pixels past the end of the batch read x = 0 but still produce an output: they must not produce a gradient
-          yn[c] = (c < out_dim && tile * 128 + wave * 32 + i < P) ? y : 0.f;
+        for (int sk = 0; sk < 2; ++sk) {
+          const float da = o0[2 * sk] + o1[2 * sk], db = o0[2 * sk + 1] + o1[2 * sk + 1];
+          const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(da), __float_as_uint(db), false, false);
+          z[sk] = (__uint_as_float(sw[0]) + __uint_as_float(sw[1])) + b2v[sk];
         }
+#pragma unroll
+        for (int sk = 0; sk < 2; ++sk) e[sk] = __builtin_amdgcn_exp2f(z[sk] * -1.4426950408889634f);
+        asm volatile("" : "+v"(e[0]), "+v"(e[1]));
+#pragma unroll
+        for (int sk = 0; sk < 2; ++sk) e[sk] = 1.0f + e[sk];
+        asm volatile("" : "+v"(e[0]), "+v"(e[1]));
+#pragma unroll
+        for (int sk = 0; sk < 2; ++sk) y[sk] = __builtin_amdgcn_rcpf(e[sk]);
+        asm volatile("" : "+v"(y[0]), "+v"(y[1]));
+        // pixels past the end of the batch read x = 0 but still produce an output: they must not produce a gradient
+        const bool live = tile * 128 + wave * 32 + i < P;
+#pragma unroll
+        for (int sk = 0; sk < 2; ++sk) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y[sk]), rs, yoffh[sk], 0, 0);
+        // Both stores are out before the first use of the targets (loaded a tile ago, the last loads in front of these stores on
+        // every path into the loop, so hipcc's count is exact): ONE vmcnt wait, behind the stores, covers both targets.
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" : "+v"(dyn[0]), "+v"(dyn[1]));
+#pragma unroll
+        for (int sk = 0; sk < 2; ++sk) yn[sk] = (2 * sk + h < out_dim && live) ? y[sk] : 0.f;
       }
       make_dz3();
       STEP_END();
@@ -875,17 +916,27 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
       float fa[2][2], bsel[2];
 #pragma unroll
       for (int sk = 0; sk < 2; ++sk) {
+        if constexpr (TRAIN) {                             // requested before the output layer; dz3[sk] IS the half's k-step operand
+          fa[0][sk] = a2t[0][sk]; fa[1][sk] = a2t[1][sk];
+          bsel[sk] = dz3[sk];
+        } else {
         fa[0][sk] = A2T[(0 * 2 + sk) * 64 + lane]; fa[1][sk] = A2T[(1 * 2 + sk) * 64 + lane];
         float lo = dz3[2 * sk], hi = dz3[2 * sk + 1];
         asm volatile("" : "+v"(lo), "+v"(hi));             // a select of two registers, not a load from a private array
         bsel[sk] = h == 0 ? lo : hi;
+        }
       }
       STEP_END();
       MFMA_VV_ZERO(d2[0], fa[0][0], bsel[0]); MFMA_VV_ZERO(d2[1], fa[1][0], bsel[0]);
       MFMA_VV(d2[0], fa[0][1], bsel[1]); MFMA_VV(d2[1], fa[1][1], bsel[1]);
+      if constexpr (TRAIN) {                               // the four products are issued: the image stores go UNDER them
+        asm volatile("" : "+v"(d2[0]), "+v"(d2[1]));
+        STEP_END();
+      }
       if constexpr (!RECOMPUTE) {                          // the images R1 / R2 would have carried
         if (BL::kDedicatedX) static_for<S0>([&](auto SX) { lds_store<kImgX + SX.value * kImgStride * 4>(wX, xr[SX.value]); });
-        static_for<4>([&](auto C) { lds_store<kImgZ + C.value * kImgStride * 4>(wDz3, dz3[C.value]); });
+        if constexpr (TRAIN) static_for<2>([&](auto SK) { lds_store<kImgZ + 2 * SK.value * kImgStride * 4>(wDz3h, dz3[SK.value]); });
+        else static_for<4>([&](auto C) { lds_store<kImgZ + C.value * kImgStride * 4>(wDz3, dz3[C.value]); });
       }
     }
     if (!RECOMPUTE && BL::kDedicatedX) fetch_x(tile + gridDim.x);
@@ -1353,7 +1404,8 @@ decoder_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Yout, 
     if (c < out_dim) sW2[c * kH + lane] = dW2acc[c];
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    float v = h == 0 ? db2acc[c] : 0.f;
+    // (TRAIN: channel c accumulated in lane half c & 1, slot c >> 1; the other half adds exact zeros either way)
+    float v = TRAIN ? (h == (c & 1) ? db2acc[c >> 1] : 0.f) : (h == 0 ? db2acc[c] : 0.f);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     if (lane == 0 && c < out_dim) sb2[c] = v;
