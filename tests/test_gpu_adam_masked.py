@@ -124,8 +124,9 @@ def test_reachable_row_map_frozen_hpd_equals_union_over_k_of_the_cached_table():
 LR, B1, B2, EPS = 1e-2, 0.9, 0.99, 1e-15
 
 
-def adam_call(p, g, m, v, master, flags, mask=None, row_elems=0, wd=0.0, steps_before=0.0, force_masked=False):
-    """one step of gngf_adam_step (mask None) or gngf_adam_step_masked over ONE segment, in place"""
+def adam_call(p, g, m, v, master, flags, mask=None, row_elems=0, wd=0.0, steps_before=0.0, force_masked=False, inv_grad_scale=1.0):
+    """one step of gngf_adam_step (mask None) or gngf_adam_step_masked over ONE segment, in place; inv_grad_scale multiplies every
+    gradient first (1 / loss scale)"""
     from collision_handling_in_instantngp_amd._lib import call, ptr, query, stream_ptr
     from collision_handling_in_instantngp_amd.train import FusedAdam
     seg = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), 0 if master is None else master.data_ptr(), p.numel(), 0, flags)
@@ -135,7 +136,7 @@ def adam_call(p, g, m, v, master, flags, mask=None, row_elems=0, wd=0.0, steps_b
     table = torch.from_numpy(raw.copy()).to(DEV)
     step = torch.full((), float(steps_before), dtype=torch.float32, device=DEV)
     lr, wdv = (ctypes.c_float * 1)(LR), (ctypes.c_float * 1)(wd)
-    args = (ptr(table), 1, blocks, ptr(step), lr, wdv, 1, B1, B2, EPS, 1.0)
+    args = (ptr(table), 1, blocks, ptr(step), lr, wdv, 1, B1, B2, EPS, float(inv_grad_scale))
     if masked:
         call("gngf_adam_step_masked", *args, ctypes.c_void_p(table.data_ptr() + 64), stream_ptr())
     else:

@@ -31,15 +31,15 @@ def case_name(leaky, P):
     return f"{'leaky' if leaky else 'relu'}/P={P}"
 
 
-def inputs(leaky, P):
-    """Seeded numpy inputs (the seed is the case itself)."""
-    rng = np.random.default_rng([7, leaky, P])
+def inputs(leaky, P, in_dim=IN_DIM):
+    """Seeded numpy inputs (the seed is the case itself; another encoder width than IN_DIM joins the seed)."""
+    rng = np.random.default_rng([7, leaky, P] + ([in_dim] if in_dim != IN_DIM else []))
     f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-    dims = [IN_DIM, 64, 64, OUT_DIM]
+    dims = [in_dim, 64, 64, OUT_DIM]
     ws = []
     for i in range(3):
         ws += [f(rng.standard_normal((dims[i + 1], dims[i])) / np.sqrt(dims[i])), f(0.1 * rng.standard_normal(dims[i + 1]))]
-    return {"enc": f(0.5 * rng.standard_normal((P, IN_DIM))), "target": f(rng.random((P, OUT_DIM))), "gloss": f([1.25]), "ws": ws}
+    return {"enc": f(0.5 * rng.standard_normal((P, in_dim))), "target": f(rng.random((P, OUT_DIM))), "gloss": f([1.25]), "ws": ws}
 
 
 def _dev(inp):
@@ -47,7 +47,23 @@ def _dev(inp):
     return t(inp["enc"]), t(inp["target"]), t(inp["gloss"]), [t(w) for w in inp["ws"]]
 
 
-def run_fused(leaky, P, inp=None):
+def _reduced(reduce, in_dim):
+    """reduce: also hand the kernel the six gradient buffers and the max |d enc| word (the slab reduction runs in the same call)"""
+    if not reduce:
+        return [None] * 6, None
+    shapes = ((64, in_dim), (64,), (64, 64), (64,), (OUT_DIM, 64), (OUT_DIM,))
+    return [torch.full(sh, -7.0, device="cuda") for sh in shapes], torch.full((1,), -7.0, device="cuda")
+
+
+def _outputs(rgb, denc, slabs, grads, absmax):
+    out = {"rgb": rgb.cpu().numpy(), "denc": denc.cpu().numpy(), "slabs": slabs.cpu().numpy()}
+    if absmax is not None:
+        out["grads"] = [g.cpu().numpy() for g in grads]
+        out["denc_absmax"] = absmax.cpu().numpy()
+    return out
+
+
+def run_fused(leaky, P, inp=None, reduce=False):
     """One gngf_decoder_train launch on fresh output buffers -> {name: numpy array} of everything it wrote."""
     from collision_handling_in_instantngp_amd._lib import call, ptr, stream_ptr, query
     enc, target, gloss, ws = _dev(inp or inputs(leaky, P))
@@ -56,27 +72,33 @@ def run_fused(leaky, P, inp=None):
     slabs = torch.full((nfl,), -7.0, device="cuda")
     rgb = torch.full((P, OUT_DIM), -7.0, device="cuda")
     denc = torch.full((P, IN_DIM), -7.0, device="cuda")
-    call("gngf_decoder_train", ptr(enc), ptr(target), ptr(gloss), *[ptr(w) for w in ws], ptr(rgb), ptr(denc), *[ptr(None)] * 6,
-         ptr(slabs), ptr(None), ptr(None), 0, P, IN_DIM, OUT_DIM, leaky, stream_ptr())
+    grads, absmax = _reduced(reduce, IN_DIM)
+    call("gngf_decoder_train", ptr(enc), ptr(target), ptr(gloss), *[ptr(w) for w in ws], ptr(rgb), ptr(denc), *[ptr(g) for g in grads],
+         ptr(slabs), ptr(absmax), ptr(None), 0, P, IN_DIM, OUT_DIM, leaky, stream_ptr())
     torch.cuda.synchronize()
-    return {"rgb": rgb.cpu().numpy(), "denc": denc.cpu().numpy(), "slabs": slabs.cpu().numpy()}
+    return _outputs(rgb, denc, slabs, grads, absmax)
 
 
-def run_two_kernels(leaky, P, inp=None):
+def run_two_kernels(leaky, P, inp=None, in_dim=IN_DIM, save_hidden=True, drgb=None, reduce=False):
     """The same quantities from gngf_decoder_fwd + gngf_decoder_bwd (all products of the forward on the fp32 pipe): equal to the
-    fused kernel to fp32 rounding, not to the bit — the yardstick a mismatch is described against."""
+    fused kernel to fp32 rounding, not to the bit — the yardstick a mismatch is described against.
+    save_hidden=False: the backward recomputes the hidden layers; drgb (P, OUT_DIM) numpy: the upstream gradient itself instead of
+    target + gloss."""
     from collision_handling_in_instantngp_amd._lib import call, ptr, stream_ptr, query
-    enc, target, gloss, ws = _dev(inp or inputs(leaky, P))
-    nfl = query("gngf_decoder_bwd_slabs", P) * query("gngf_decoder_slab_floats", IN_DIM, OUT_DIM)
+    enc, target, gloss, ws = _dev(inp or inputs(leaky, P, in_dim))
+    nfl = query("gngf_decoder_bwd_slabs", P) * query("gngf_decoder_slab_floats", in_dim, OUT_DIM)
     slabs = torch.full((nfl,), -7.0, device="cuda")
-    hidden = torch.empty((query("gngf_decoder_hidden_floats", P),), device="cuda")
+    hidden = torch.empty((query("gngf_decoder_hidden_floats", P),), device="cuda") if save_hidden else None
     rgb = torch.full((P, OUT_DIM), -7.0, device="cuda")
-    denc = torch.full((P, IN_DIM), -7.0, device="cuda")
-    call("gngf_decoder_fwd", ptr(enc), *[ptr(w) for w in ws], ptr(rgb), ptr(hidden), P, IN_DIM, OUT_DIM, leaky, stream_ptr())
-    call("gngf_decoder_bwd", ptr(enc), ptr(rgb), ptr(None), ptr(target), ptr(gloss), *[ptr(w) for w in ws[:5]], ptr(denc),
-         *[ptr(None)] * 6, ptr(slabs), ptr(None), ptr(hidden), ptr(None), 0, P, IN_DIM, OUT_DIM, leaky, stream_ptr())
+    denc = torch.full((P, in_dim), -7.0, device="cuda")
+    grads, absmax = _reduced(reduce, in_dim)
+    d = None if drgb is None else torch.from_numpy(np.ascontiguousarray(drgb, dtype=np.float32)).cuda()
+    call("gngf_decoder_fwd", ptr(enc), *[ptr(w) for w in ws], ptr(rgb), ptr(hidden), P, in_dim, OUT_DIM, leaky, stream_ptr())
+    call("gngf_decoder_bwd", ptr(enc), ptr(rgb), ptr(d), ptr(None if d is not None else target), ptr(None if d is not None else gloss),
+         *[ptr(w) for w in ws[:5]], ptr(denc), *[ptr(g) for g in grads], ptr(slabs), ptr(absmax), ptr(hidden), ptr(None), 0, P, in_dim,
+         OUT_DIM, leaky, stream_ptr())
     torch.cuda.synchronize()
-    return {"rgb": rgb.cpu().numpy(), "denc": denc.cpu().numpy(), "slabs": slabs.cpu().numpy()}
+    return _outputs(rgb, denc, slabs, grads, absmax)
 
 
 def digest(a):
