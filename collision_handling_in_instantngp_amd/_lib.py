@@ -135,9 +135,12 @@ EXT3_SIGNATURES = {
     "gngf_ext3_version": [],
     "gngf_ext3_query": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _I, _L, _I, _I] + _QUERY_TAIL,
     "gngf_ext3_query_grid": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I] + _QUERY_TAIL,
+    # (version 2) gngf_vertex_grid_bwd_flat's arguments; gngf_encode_tiled_bwd's, then (clear_base, clear_rows, n_clear_rows) before the stream
+    "gngf_ext3_vertex_grid_bwd_flat_owned": list(SIGNATURES["gngf_vertex_grid_bwd_flat"]),
+    "gngf_ext3_encode_tiled_bwd_clear_rows": SIGNATURES["gngf_encode_tiled_bwd"][:-1] + [_P, _P, _I, _P],
 }
 
-EXT3_VERSION = 1
+EXT3_VERSION = 2
 
 # entry points of include/gngf_ext3.h that take no writable pointer: name -> why no guard-band case is owed
 EXT3_WRITES_NOTHING = {

@@ -16,6 +16,7 @@
 // workgroup once per touched vertex instead of once per (pixel, corner): the 134 M global float atomics of the
 // direct form become ~2 M row-contiguous ones.
 #include "gngf_common.h"
+#include "../../include/gngf_ext3.h"
 
 namespace gngf {
 
@@ -606,6 +607,15 @@ struct MseRide {
   unsigned* counter;
   int64_t n;
   int first_block, nblocks;
+};
+
+// A sparse row clear riding on the interleaved backward's launch (gngf_ext3_encode_tiled_bwd_clear_rows): workgroups from
+// first_block on store zeros to rows[i] of `base` (F floats each), one row per thread.  The launch itself never touches `base`;
+// the rows are the ones the next launch of the chain adds to with atomics.  rows == nullptr: none.
+struct RowClear {
+  float* base;
+  const int32_t* rows;
+  int n, F, first_block;
 };
 
 struct TileMeta {          // per-level placement of the tile's sub-grid (in LDS)
@@ -1301,12 +1311,22 @@ tiled_bwd_il_kernel(const float4* __restrict__ sorted, const int4* __restrict__ 
                     float* __restrict__ dG, float* __restrict__ partials, const float* __restrict__ gmax_hint, int hint_count,
                     int hint_stride, int L, int Ls, int tile_shift, int lds_floats, int rows2, int log2_chunk, int nwork,
                     RideAlong ride, MseRide mride, unsigned long long* __restrict__ dG64, const BinJobDev bride,
-                    float* __restrict__ hash_dt = nullptr, int64_t hash_T = 0, bool hash_pow2 = false) {
+                    float* __restrict__ hash_dt = nullptr, int64_t hash_T = 0, bool hash_pow2 = false,
+                    const RowClear rclear = RowClear{nullptr, nullptr, 0, 0, 0}) {
   constexpr int F = 2;
   extern __shared__ unsigned long long accil[];   // [rows2][kIL], then the compact fp32 image of the store pass
   __shared__ ILMeta m;
   __shared__ float wmax[kTB / 64];
   __shared__ int s_task;
+  if (rclear.rows && (int)blockIdx.x >= rclear.first_block) {           // (the last riders of the launch)
+    const int i = ((int)blockIdx.x - rclear.first_block) * kTB + (int)threadIdx.x;
+    if (i < rclear.n) {
+      const int r = rclear.rows[i];
+      if (r >= 0)
+        for (int f = 0; f < rclear.F; ++f) rclear.base[(int64_t)r * rclear.F + f] = 0.f;
+    }
+    return;
+  }
   if (mride.pred && (int)blockIdx.x >= mride.first_block) {
     mse_sum_block((int)blockIdx.x - mride.first_block, mride.nblocks, mride.pred, mride.label, mride.loss, mride.acc, mride.counter,
                   mride.n);
@@ -1909,166 +1929,28 @@ vertex_bwd_sorted_kernel(const TT* __restrict__ tables, const int32_t* __restric
   if (live && dvert_w) dvert_w[e] = dw_acc;
 }
 
-// Vertex stage backward over a STATIC item list (frozen vertex table, no d w): everything vertex_bwd_sorted_kernel resolves
-// per step — order -> (vert_idx, vert_w) -> levels -> grid position, and where the equal-slot runs lie — is fixed between
-// two table builds, so ops.vertex_flat_list resolves it once: one item per (level, vertex, k) = (gi: index into the vertex
-// grid, w, dest: l * T + slot), sorted by dest.  The kernel is one flat segmented reduction: no level loop, no per-level
-// barrier, one gather per item with all of a thread's gathers in flight together.
-//   thread     kFlatIPT consecutive items (wide loads of gi / w / dest); runs that lie wholly inside it: one atomic each
-//   workgroup  the threads' open head / tail partials meet in ONE segmented scan (wave shuffles, then LDS across waves);
-//              one atomic per run that ends in, or crosses, the workgroup — no address gets more than one add per workgroup
-// The value of an item is formed exactly as vertex_bwd_sorted_kernel forms it (poison flag included).
-// measured at the headline shape (2.87 M items, us per launch): 256 threads x 4 items 16.2 | 512 x 4: 16.3 | 128 x 4: 19.9 |
-// 256 x 8: 19.7 | 128 x 8: 19.1; gathering a vertex's two 64-bit words in one 16-byte load instead of two 8-byte ones: 16.2 vs 16.4
-// (no gain: not kept)
-constexpr int kFlatTB = 256;       // threads per workgroup
-constexpr int kFlatIPT = 4;        // items per thread (one 16-byte load per static array)
-static_assert(kFlatIPT % 4 == 0 && kFlatTB % 64 == 0, "whole 16-byte loads, whole waves");
+// Vertex stage backward over a STATIC item list (frozen vertex table, no d w): the flat segmented reduction of vertex_flat.inc,
+// every run ADDED to its row of a zeroed table gradient (one atomic per run and workgroup).
+#include "vertex_flat.inc"
 template <int F, bool FROM64>
 __global__ void __launch_bounds__(kFlatTB)
 vertex_bwd_flat_kernel(const int32_t* __restrict__ item_gi, const float* __restrict__ item_w, const int32_t* __restrict__ item_dest,
                        int64_t N, const float* __restrict__ dG, const unsigned long long* __restrict__ dG64, int64_t vtot,
                        float* __restrict__ dtables, int64_t rows) {
-  constexpr int NW = kFlatTB / 64;
-  __shared__ int s_firstd[kFlatTB], s_lastd[kFlatTB];
-  __shared__ float s_y[kFlatTB][F];
-  __shared__ float s_wtot[NW][F];
-  __shared__ int s_wflag[NW];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t i0 = ((int64_t)blockIdx.x * kFlatTB + tid) * kFlatIPT;
+  const int64_t i0 = ((int64_t)blockIdx.x * kFlatTB + threadIdx.x) * kFlatIPT;
   int gi[kFlatIPT], d[kFlatIPT];
   float w[kFlatIPT];
-  if (i0 + kFlatIPT <= N) {
-#pragma unroll
-    for (int c = 0; c < kFlatIPT; c += 4) {
-      const int4 g4 = *reinterpret_cast<const int4*>(item_gi + i0 + c);
-      const float4 w4 = *reinterpret_cast<const float4*>(item_w + i0 + c);
-      const int4 d4 = *reinterpret_cast<const int4*>(item_dest + i0 + c);
-      gi[c] = g4.x; gi[c + 1] = g4.y; gi[c + 2] = g4.z; gi[c + 3] = g4.w;
-      w[c] = w4.x; w[c + 1] = w4.y; w[c + 2] = w4.z; w[c + 3] = w4.w;
-      d[c] = d4.x; d[c + 1] = d4.y; d[c + 2] = d4.z; d[c + 3] = d4.w;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < kFlatIPT; ++i) {                     // the ragged end; items past it: dest -1, which is never emitted
-      const bool on = i0 + i < N;
-      gi[i] = on ? item_gi[i0 + i] : 0;
-      w[i] = on ? item_w[i0 + i] : 0.f;
-      d[i] = on ? item_dest[i0 + i] : -1;
-    }
-  }
-  // every gather of the thread is issued before the first one is used.  (The list is checked on the host when it is built;
-  // the clamp keeps a list that was not from reading outside the grid.)
+  flat_load_items(item_gi, item_w, item_dest, N, i0, gi, w, d);
   float v[kFlatIPT][F];
-  if constexpr (FROM64) {
-    unsigned long long q[kFlatIPT][F];
-#pragma unroll
-    for (int i = 0; i < kFlatIPT; ++i) {
-      const int64_t g = gi[i] < 0 ? 0 : (gi[i] < vtot ? gi[i] : vtot - 1);
-#pragma unroll
-      for (int f = 0; f < F; ++f) q[i][f] = dG64[g * F + f];
-    }
-    const double inv64 = ldexp(1.0, -(int)(long long)dG64[vtot * F]);
-    const bool poisoned = dG64[vtot * F + 1] != 0ull;
-#pragma unroll
-    for (int i = 0; i < kFlatIPT; ++i)
-#pragma unroll
-      for (int f = 0; f < F; ++f)
-        v[i][f] = (poisoned ? __int_as_float(0x7fc00000) : (float)((double)(long long)q[i][f] * inv64)) * w[i];   // as vertex_bwd_sorted_kernel
-  } else {
-    float q[kFlatIPT][F];
-#pragma unroll
-    for (int i = 0; i < kFlatIPT; ++i) {
-      const int64_t g = gi[i] < 0 ? 0 : (gi[i] < vtot ? gi[i] : vtot - 1);
-#pragma unroll
-      for (int f = 0; f < F; ++f) q[i][f] = dG[g * F + f];
-    }
-#pragma unroll
-    for (int i = 0; i < kFlatIPT; ++i)
-#pragma unroll
-      for (int f = 0; f < F; ++f) v[i][f] = q[i][f] * w[i];
-  }
-  auto emit = [&](int dest, const float* s) {
+  flat_item_values<F, FROM64>(gi, w, dG, dG64, vtot, v);
+  flat_segmented_reduce<F>(d, v, [&](int dest, const float* s) {
     if ((uint64_t)(int64_t)dest < (uint64_t)rows) {          // (dest -1: items past the end of the list)
       float* p = dtables + (int64_t)dest * F;
 #pragma unroll
       for (int f = 0; f < F; ++f)
         if (s[f] != 0.f) atomicAdd(p + f, s[f]);
     }
-  };
-  // the thread's own runs: the first one (head) and the last one (tail, = the head when there is no boundary inside the
-  // thread) stay open; the ones in between are complete
-  float acc[F], head[F];
-  int nb = 0;
-#pragma unroll
-  for (int f = 0; f < F; ++f) { acc[f] = v[0][f]; head[f] = 0.f; }
-#pragma unroll
-  for (int i = 1; i < kFlatIPT; ++i) {
-    if (d[i] != d[i - 1]) {
-      if (nb == 0) {
-#pragma unroll
-        for (int f = 0; f < F; ++f) head[f] = acc[f];
-      } else {
-        emit(d[i - 1], acc);
-      }
-      ++nb;
-#pragma unroll
-      for (int f = 0; f < F; ++f) acc[f] = v[i][f];
-    } else {
-#pragma unroll
-      for (int f = 0; f < F; ++f) acc[f] += v[i][f];
-    }
-  }
-  s_firstd[tid] = d[0];
-  s_lastd[tid] = d[kFlatIPT - 1];
-  __syncthreads();
-  const int prev_d = tid > 0 ? s_lastd[tid - 1] : -2;                   // (-2: equal to no dest, not even a dead item's)
-  const int next_d = tid + 1 < kFlatTB ? s_firstd[tid + 1] : -2;
-  // inclusive segmented scan of the tail partials over the workgroup's threads; a thread STARTS a segment when its tail run
-  // begins inside it, or at its first item
-  const int starts = (nb > 0 || prev_d != d[0]) ? 1 : 0;
-  float y[F];
-  int flag = starts;
-#pragma unroll
-  for (int f = 0; f < F; ++f) y[f] = acc[f];
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int fu = __shfl_up(flag, o, 64);
-    float yu[F];
-#pragma unroll
-    for (int f = 0; f < F; ++f) yu[f] = __shfl_up(y[f], o, 64);
-    if (lane >= o) {
-      if (!flag) {
-#pragma unroll
-        for (int f = 0; f < F; ++f) y[f] += yu[f];
-      }
-      flag |= fu;
-    }
-  }
-  if (lane == 63) {                                                      // the wave's open tail, and whether a segment starts in it
-#pragma unroll
-    for (int f = 0; f < F; ++f) s_wtot[wave][f] = y[f];
-    s_wflag[wave] = flag;
-  }
-  __syncthreads();
-  if (!flag) {                                                           // no segment has started in this wave up to this lane: the
-    for (int q = wave - 1; q >= 0; --q) {                                // run comes in from the waves below
-#pragma unroll
-      for (int f = 0; f < F; ++f) y[f] += s_wtot[q][f];
-      if (s_wflag[q]) break;
-    }
-  }
-#pragma unroll
-  for (int f = 0; f < F; ++f) s_y[tid][f] = y[f];
-  __syncthreads();
-  if (nb > 0) {                                                          // my head run ends inside me
-    if (tid > 0 && prev_d == d[0]) {
-#pragma unroll
-      for (int f = 0; f < F; ++f) head[f] += s_y[tid - 1][f];
-    }
-    emit(d[0], head);
-  }
-  if (next_d != d[kFlatIPT - 1]) emit(d[kFlatIPT - 1], y);               // my tail run ends with me (or leaves the workgroup)
+  });
 }
 
 }  // namespace gngf
@@ -2430,17 +2312,25 @@ extern "C" int gngf_encode_tiled_fwd_fused(const float* sorted, const int32_t* i
   GNGF_RETURN_LAUNCH();
 }
 
-extern "C" int gngf_encode_tiled_bwd(const float* sorted, const int32_t* items, const int32_t* n_items, int max_items,
-                                     const int32_t* tile_item_base, const int32_t* tile_level_off, const int32_t* n_ls,
-                                     const int32_t* n_ls_host, const float* genc, const float* genc_absmax, int absmax_count,
-                                     int absmax_stride, float* dG, float* partials, int L, int Ls, int F, int tile_shift,
-                                     int lds_bytes, int chunk, const float* ride_slabs, float* ride_dW0, float* ride_db0,
-                                     float* ride_dW1, float* ride_db1, float* ride_dW2, float* ride_db2, int64_t ride_P,
-                                     int ride_in_dim, int ride_out_dim, const float* gloss_promised, const float* gloss_arrived,
-                                     const float* mse_pred, const float* mse_label,
-                                     float* mse_loss, float* mse_workspace, int64_t mse_n, float* hash_dtables, int64_t hash_T,
-                                     void* dG64, int log2_pixels, const gngf_bin_job* next_bin, void* stream) {
+// The launcher behind gngf_encode_tiled_bwd and gngf_ext3_encode_tiled_bwd_clear_rows.  clear_rows (n_clear_rows int32 row numbers,
+// rows of F floats in clear_base): zeroed by rider workgroups of the interleaved kernel's launch; n_clear_rows == 0: no such rider,
+// the launch is gngf_encode_tiled_bwd's as it always was.
+static int launch_tiled_bwd(const float* sorted, const int32_t* items, const int32_t* n_items, int max_items,
+                            const int32_t* tile_item_base, const int32_t* tile_level_off, const int32_t* n_ls,
+                            const int32_t* n_ls_host, const float* genc, const float* genc_absmax, int absmax_count,
+                            int absmax_stride, float* dG, float* partials, int L, int Ls, int F, int tile_shift,
+                            int lds_bytes, int chunk, const float* ride_slabs, float* ride_dW0, float* ride_db0,
+                            float* ride_dW1, float* ride_db1, float* ride_dW2, float* ride_db2, int64_t ride_P,
+                            int ride_in_dim, int ride_out_dim, const float* gloss_promised, const float* gloss_arrived,
+                            const float* mse_pred, const float* mse_label,
+                            float* mse_loss, float* mse_workspace, int64_t mse_n, float* hash_dtables, int64_t hash_T,
+                            void* dG64, int log2_pixels, const gngf_bin_job* next_bin, float* clear_base, const int32_t* clear_rows,
+                            int n_clear_rows, void* stream) {
   GNGF_CHECK_ARG(!hash_dtables || hash_T > 0);
+  // the row-clear rider exists in the interleaved kernel only, and only beside work items
+  GNGF_CHECK_ARG(n_clear_rows >= 0 && n_clear_rows <= (1 << 24));
+  GNGF_CHECK_ARG(n_clear_rows == 0 || (clear_base && clear_rows && max_items > 0 && n_ls_host && (F == 1 || F == 2 || F == 4 || F == 8) &&
+                                       interleaved_applies(n_ls_host, Ls, F, tile_shift, lds_bytes / 4, true)));
   // the scatter half of another batch's binning rides in the tail of the persistent interleaved kernel only
   BinJobDev bride = bin_job_none();
   GNGF_CHECK_ARG(!next_bin || (bin_job_dev(next_bin, true, &bride) && max_items > 0 && n_ls_host &&
@@ -2507,10 +2397,13 @@ extern "C" int gngf_encode_tiled_bwd(const float* sorted, const int32_t* items, 
     if (mse_pred) mride.first_block = nwork + (ride_slabs ? (ride.nslab + 63) / 64 : 0);
     // one scale for the launch (a bound on |genc| from its producer) -> the items add their sums into a fixed-point vertex grid
     unsigned long long* g64 = (genc_absmax && dG64 && log2_pixels > 0 && log2_pixels <= 40) ? static_cast<unsigned long long*>(dG64) : nullptr;
-    fn<<<dim3((unsigned)(nwork + ride_blocks)), dim3(kTB), smem, as_stream(stream)>>>(
+    const RowClear rclear = {n_clear_rows > 0 ? clear_base : nullptr, n_clear_rows > 0 ? clear_rows : nullptr, n_clear_rows, F,
+                             nwork + ride_blocks};
+    const int clear_blocks = (n_clear_rows + kTB - 1) / kTB;
+    fn<<<dim3((unsigned)(nwork + ride_blocks + clear_blocks)), dim3(kTB), smem, as_stream(stream)>>>(
         reinterpret_cast<const float4*>(sorted), reinterpret_cast<const int4*>(items), n_items, const_cast<int32_t*>(n_items) + 2, n_ls,
         genc, dG, partials, genc_absmax, absmax_count, absmax_stride, L, Ls, tile_shift, lds_bytes / 4, rows2,
-        g64 ? log2_pixels : log2_chunk, nwork, ride, mride, g64, bride, hdt ? hash_dtables : nullptr, hash_T, hpow2);
+        g64 ? log2_pixels : log2_chunk, nwork, ride, mride, g64, bride, hdt ? hash_dtables : nullptr, hash_T, hpow2, rclear);
     if (hdt) GNGF_RETURN_LAUNCH();
     if (g64) {
       if (dG)        // (dG NULL: the caller's vertex stage reads the fixed-point grid itself — gngf_vertex_grid_bwd_sorted(dG64))
@@ -2550,6 +2443,39 @@ extern "C" int gngf_encode_tiled_bwd(const float* sorted, const int32_t* items, 
     }
   });
   GNGF_RETURN_LAUNCH();
+}
+
+extern "C" int gngf_encode_tiled_bwd(const float* sorted, const int32_t* items, const int32_t* n_items, int max_items,
+                                     const int32_t* tile_item_base, const int32_t* tile_level_off, const int32_t* n_ls,
+                                     const int32_t* n_ls_host, const float* genc, const float* genc_absmax, int absmax_count,
+                                     int absmax_stride, float* dG, float* partials, int L, int Ls, int F, int tile_shift,
+                                     int lds_bytes, int chunk, const float* ride_slabs, float* ride_dW0, float* ride_db0,
+                                     float* ride_dW1, float* ride_db1, float* ride_dW2, float* ride_db2, int64_t ride_P,
+                                     int ride_in_dim, int ride_out_dim, const float* gloss_promised, const float* gloss_arrived,
+                                     const float* mse_pred, const float* mse_label,
+                                     float* mse_loss, float* mse_workspace, int64_t mse_n, float* hash_dtables, int64_t hash_T,
+                                     void* dG64, int log2_pixels, const gngf_bin_job* next_bin, void* stream) {
+  return launch_tiled_bwd(sorted, items, n_items, max_items, tile_item_base, tile_level_off, n_ls, n_ls_host, genc, genc_absmax,
+                          absmax_count, absmax_stride, dG, partials, L, Ls, F, tile_shift, lds_bytes, chunk, ride_slabs, ride_dW0, ride_db0,
+                          ride_dW1, ride_db1, ride_dW2, ride_db2, ride_P, ride_in_dim, ride_out_dim, gloss_promised, gloss_arrived,
+                          mse_pred, mse_label, mse_loss, mse_workspace, mse_n, hash_dtables, hash_T, dG64, log2_pixels, next_bin,
+                          nullptr, nullptr, 0, stream);
+}
+
+// gngf_encode_tiled_bwd with the row-clear rider (include/gngf_ext3.h)
+extern "C" int gngf_ext3_encode_tiled_bwd_clear_rows(
+    const float* sorted, const int32_t* items, const int32_t* n_items, int max_items, const int32_t* tile_item_base,
+    const int32_t* tile_level_off, const int32_t* n_ls, const int32_t* n_ls_host, const float* genc, const float* genc_absmax,
+    int absmax_count, int absmax_stride, float* dG, float* partials, int L, int Ls, int F, int tile_shift, int lds_bytes, int chunk,
+    const float* ride_slabs, float* ride_dW0, float* ride_db0, float* ride_dW1, float* ride_db1, float* ride_dW2, float* ride_db2,
+    int64_t ride_P, int ride_in_dim, int ride_out_dim, const float* gloss_promised, const float* gloss_arrived, const float* mse_pred,
+    const float* mse_label, float* mse_loss, float* mse_workspace, int64_t mse_n, float* hash_dtables, int64_t hash_T, void* dG64,
+    int log2_pixels, const gngf_bin_job* next_bin, float* clear_base, const int32_t* clear_rows, int n_clear_rows, void* stream) {
+  return launch_tiled_bwd(sorted, items, n_items, max_items, tile_item_base, tile_level_off, n_ls, n_ls_host, genc, genc_absmax,
+                          absmax_count, absmax_stride, dG, partials, L, Ls, F, tile_shift, lds_bytes, chunk, ride_slabs, ride_dW0, ride_db0,
+                          ride_dW1, ride_db1, ride_dW2, ride_db2, ride_P, ride_in_dim, ride_out_dim, gloss_promised, gloss_arrived,
+                          mse_pred, mse_label, mse_loss, mse_workspace, mse_n, hash_dtables, hash_T, dG64, log2_pixels, next_bin,
+                          clear_base, clear_rows, n_clear_rows, stream);
 }
 
 // Vertex stage backward, vertex-table source, slot-ordered and contention-free (see vertex_bwd_sorted_kernel).

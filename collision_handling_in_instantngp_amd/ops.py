@@ -347,6 +347,37 @@ def _persistent_peek(dp, tables):
     return buf
 
 
+def _owned_peek(dp, tables, flat):
+    """The model's step-to-step table-gradient buffer for the frozen table whose item list is `flat` (ops.VERTEX_BWD_OWNED), if it
+    is free right now — else None.  A (L, T, F) fp32 tensor on dp, apart from dp.persist_grad; zeroed when it is made and whenever
+    it is to serve another list (a rebuilt table, another staged level count: rows the old list reached and the new one does not
+    must read zero), never inside a capture (there such a change gets None: the parent's chain).  Free: the rule of
+    _persistent_peek — the loop opted in (dp.persist_ok) and no level parameter's .grad / .grad_fp32 lives in the buffer."""
+    params = getattr(dp, "level_params", None) if dp is not None else None
+    if not params or not getattr(dp, "persist_ok", False) or dp.exchange is not None or flat is None or flat.cross is None:
+        return None
+    if tables.dtype != _f32 or not tables.is_cuda:
+        return None
+    buf = getattr(dp, "owned_grad", None)
+    fits = buf is not None and tuple(buf.shape) == tuple(tables.shape) and buf.device == tables.device
+    if fits:
+        base = buf.untyped_storage().data_ptr()
+        for w in params:
+            for g in (w.grad, getattr(w, "grad_fp32", None)):
+                if g is not None and g.is_cuda and g.untyped_storage().data_ptr() == base:
+                    return None                           # the previous gradient has not been let go of: it stays intact
+        if getattr(dp, "owned_for", None) is flat:
+            return buf
+    if torch.cuda.is_current_stream_capturing():
+        return None                                       # (a buffer is neither born nor re-zeroed inside a capture)
+    if fits:
+        buf.zero_()                                       # the same shape, another list
+    else:
+        buf = dp.owned_grad = torch.zeros(tuple(tables.shape), dtype=_f32, device=tables.device)
+    dp.owned_for = flat
+    return buf
+
+
 def _persistent_grad(dp, tables, plan, n_ls, cleared=None):
     """the buffer for a backward pass, staged levels' rows cleared — or None (in use / cannot be allocated here).
     cleared: the generation at which this pass's FORWARD had the vertex riders clear those rows (TiledWorkspace(clear_rows=)):
@@ -1044,6 +1075,8 @@ class DataParallel:
         self.persist_ok = False         # the loop's owner vouches that no gradient older than the current step is kept (opt-in)
         self.persist_grad = None        # the step-to-step table-gradient buffer (ops.PERSISTENT_TABLE_GRAD)
         self.persist_gen = 0            # ... and how often it has been handed to a backward pass (or re-allocated)
+        self.owned_grad = None          # the step-to-step buffer whose rows the flat vertex backward stores (ops.VERTEX_BWD_OWNED)
+        self.owned_for = None           # ... and the VertexFlatList it serves (another one: zeroed again, outside a capture)
         self.pipeline = BinPipeline()   # the next batch's binning riding on this step's pixel-stage launches
         self.step_config = None         # the StepConfig of the model's most recent forward pass through the fused encoder
         self.zero = None                # parallel.shard_direct_levels: this rank's share of the direct levels' rows
@@ -1328,6 +1361,15 @@ def slot_order(vert_idx, n_ls_host=None, vstride=None):
 # VERTEX_BWD_FLAT (default 1) — frozen vertex table, no d w: the vertex stage backward runs over a static item list built once per
 # table (vertex_flat_list; gngf_vertex_grid_bwd_flat).  0: the slot-ordered kernel, as for every other case (A/B from one build).
 VERTEX_BWD_FLAT = 1
+# VERTEX_BWD_OWNED (default 1) — on top of the flat list, in a loop that opted in (dp.persist_ok): the table gradient lives in ONE
+# buffer from step to step and the flat kernel STORES every row whose run lies inside one of its workgroups
+# (gngf_ext3_vertex_grid_bwd_flat_owned), so nobody clears the (L, T, F) buffer: the rows a frozen table can reach are the same every
+# step, all other rows stay zero from the day the buffer was made.  Only the rows of runs that cross a workgroup boundary
+# (VertexFlatList.cross) are still added to with atomics; rider workgroups of the pixel-stage backward's launch clear those.
+# 0: the parent chain — [dE | dG64] in one allocation, cleared whole by the training decoder (A/B from one build).
+VERTEX_BWD_OWNED = 1
+# items per workgroup of the flat kernels (csrc/vertex_flat.inc: kFlatTB * kFlatIPT)
+FLAT_BLOCK_ITEMS = 1024
 # No list above this many items (12 bytes each: 48 MiB at the cap): the slot-ordered kernel runs instead.  The headline shape has
 # 2 866 176 items = 33 MiB beside 64 MiB of level tables; shapes whose vertex grids outgrow the cap (n_max 4096: 25 M vertices)
 # would pay more for reading the list than the per-step resolution it saves.
@@ -1344,6 +1386,20 @@ class VertexFlatList:
     Ls: int
     T: int
     vtot: int
+    cross: object = None   # (n_cross,) int32: dest of every run that touches more than one block of FLAT_BLOCK_ITEMS items, ascending
+
+
+def flat_crossing_rows(dest, block=None):
+    """The dest of every run of equal values in the ascending `dest` that touches more than one block of `block` consecutive items
+    (a flat kernel's workgroup): the rows gngf_ext3_vertex_grid_bwd_flat_owned adds to instead of storing.  One candidate per block
+    boundary — items b - 1 and b = k * block of the same run — each row listed once.  int32, ascending."""
+    block = FLAT_BLOCK_ITEMS if block is None else int(block)
+    n = dest.numel()
+    if n <= block:
+        return torch.empty((0,), dtype=_i32, device=dest.device)
+    b = torch.arange(block, n, block, device=dest.device, dtype=_i64)
+    after = dest[b]
+    return torch.unique(after[dest[b - 1] == after]).to(_i32).contiguous()
 
 
 def vertex_flat_list(vert_idx, vert_w, n_ls_host, vstride, T):
@@ -1381,7 +1437,10 @@ def vertex_flat_list(vert_idx, vert_w, n_ls_host, vstride, T):
     assert gi.numel() == w.numel() == dest.numel() == n
     if int(gi.min()) < 0 or int(gi.max()) >= vtot or int(dest[0]) < 0 or int(dest[-1]) >= Ls * T:
         raise ValueError("vertex_flat_list: an index left its range")
-    return VertexFlatList(gi.to(_i32).contiguous(), w.contiguous(), dest.to(_i32).contiguous(), n, Ls, T, vtot)
+    cross = flat_crossing_rows(dest)
+    if cross.numel() > (n - 1) // FLAT_BLOCK_ITEMS or (cross.numel() and (int(cross[0]) < 0 or int(cross[-1]) >= Ls * T)):
+        raise ValueError("vertex_flat_list: a crossing row left its range")
+    return VertexFlatList(gi.to(_i32).contiguous(), w.contiguous(), dest.to(_i32).contiguous(), n, Ls, T, vtot, cross)
 
 
 class VertexFlatLists:
@@ -1444,7 +1503,7 @@ def tile_level_offsets(plan, device):
 
 # The kernel chain of one training step at the headline shape, as a string that changes whenever the chain does: PMC traffic
 # figures (profiles/traffic.json) are stamped with it and bench.py reports them only for the chain they were measured on.
-STEP_CHAIN_SIGNATURE = "r6: [bin_count_ride+bin_scatter2 | riders of the previous step] > tiled_fwd_il<SRC tables>(+count riders) > decoder_train > tiled_bwd_il(+scatter tasks, reduce, mse)<hash: HDT, table rows added by the store pass> [> vertex_bwd_flat<FROM64> over the static item list of the frozen table (vertex-table source; vertex_bwd_sorted<FROM64> without a list)]"
+STEP_CHAIN_SIGNATURE = "r7: [bin_count_ride+bin_scatter2 | riders of the previous step] > tiled_fwd_il<SRC tables>(+count riders) > decoder_train > tiled_bwd_il(+scatter tasks, reduce, mse)<hash: HDT, table rows added by the store pass> [> vertex_bwd_flat<FROM64> over the static item list of the frozen table (vertex-table source; vertex_bwd_sorted<FROM64> without a list; vertex_bwd_flat_owned<FROM64> in a loop that opted in: rows stored into a step-to-step buffer, decoder_train clears dG64 only, crossing rows cleared by riders of tiled_bwd_il)]"
 # TUNING.fused_vertex_fwd (default True)      — fp32 tables on the interleaved forward kernel: the vertex stage forward runs inside its staging loop
 # TUNING.bin_pipeline (default True)          — ... and an announced next batch (BinPipeline) is binned by riders of this step's pixel-stage launches
 # F = 2, <= 16 staged levels, bounded |genc| (every source but the single-rank hash one below): the interleaved backward adds into a
@@ -1459,9 +1518,10 @@ STEP_CHAIN_SIGNATURE = "r6: [bin_count_ride+bin_scatter2 | riders of the previou
 PIXEL_BWD_TRACE = None       # tests: a list that receives one record per pixel-stage backward launch (which chain ran)
 
 
-def _pixel_bwd(plan, ws, n_ls, genc, dG, L, F, absmax=None, link=None, hash_fuse=None, dG64=None, next_bin=None):
+def _pixel_bwd(plan, ws, n_ls, genc, dG, L, F, absmax=None, link=None, hash_fuse=None, dG64=None, next_bin=None, clear=None):
     """absmax: None or (tensor, count, stride) — `count` floats `stride` apart whose maximum bounds |genc|.
-    link: the StepLink of the forward pass (decoder slab reduction / loss value waiting for a launch to ride on, promise)."""
+    link: the StepLink of the forward pass (decoder slab reduction / loss value waiting for a launch to ride on, promise).
+    clear: None or (base, rows) — rider workgroups of the (level-interleaved) launch zero row rows[i] (F floats) of base."""
     if PIXEL_BWD_TRACE is not None:
         PIXEL_BWD_TRACE.append({"P": plan.P, "Ls": plan.Ls, "bound": absmax is not None, "dG64": dG64 is not None and absmax is not None,
                                 "hash_fuse": hash_fuse is not None, "fp32_grid": dG is not None,
@@ -1487,7 +1547,11 @@ def _pixel_bwd(plan, ws, n_ls, genc, dG, L, F, absmax=None, link=None, hash_fuse
     ride_args += [ptr(dG64, _i64, "dG64"), max(1, int(plan.P - 1).bit_length())] if dG64 is not None else [ptr(None), 0]
     # next_bin: gngf_bin_job of the NEXT batch — its scatter half runs as tasks in the tail of this launch (BinPipeline)
     ride_args += [_ct.byref(next_bin) if next_bin is not None else None]
-    call("gngf_encode_tiled_bwd", ptr(ws.sorted), ptr(ws.items), ptr(ws.n_items), plan.max_items, ptr(ws.tile_item_base),
+    entry = "gngf_encode_tiled_bwd"
+    if clear is not None and clear[1].numel() > 0:
+        entry = "gngf_ext3_encode_tiled_bwd_clear_rows"
+        ride_args += [ptr(clear[0], _f32, "clear_base"), ptr(clear[1], _i32, "clear_rows"), int(clear[1].numel())]
+    call(entry, ptr(ws.sorted), ptr(ws.items), ptr(ws.n_items), plan.max_items, ptr(ws.tile_item_base),
          ptr(tile_level_offsets(plan, genc.device)), ptr(n_ls), plan.n_ls_c, ptr(genc, _f32, "grad"), ptr(am),
          int(am_count), int(am_stride), ptr(dG), ptr(partials), L, plan.Ls, F, plan.tile_shift, plan.lds_bytes, plan.chunk,
          *ride_args, stream_ptr())
@@ -1520,16 +1584,20 @@ def _flat_list_of(order, plan, vert_idx, vert_w, T):
     return lists.get(plan.Ls, vert_idx, vert_w, T)
 
 
-def _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw, order=None, dG64=None, flat=None, mode=None):
+def _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw, order=None, dG64=None, flat=None, mode=None, owned=False):
     """dG64: the fixed-point vertex grid of _pixel_bwd(..., dG=None, dG64=...) read directly (slot-ordered and flat forms only).
-    flat: the VertexFlatList of this (frozen) table for levels [0, plan.Ls) — without d w the flat segmented reduction runs."""
+    flat: the VertexFlatList of this (frozen) table for levels [0, plan.Ls) — without d w the flat segmented reduction runs.
+    owned: dtables is the step-to-step buffer of that list (rows of flat.cross zeroed): the flat kernel that stores its rows runs."""
     L, T, F = tables.shape
     if flat is not None and dvw is None and VERTEX_BWD_FLAT and vert_idx is not None and order is not None:
         if (flat.Ls, flat.T, flat.vtot) != (plan.Ls, T, plan.vtot):
             raise ValueError(f"the item list is for {flat.Ls} levels of {flat.T} rows, {flat.vtot} vertices: not this plan's")
-        call("gngf_vertex_grid_bwd_flat", ptr(flat.gi, _i32, "item_gi"), ptr(flat.w, _f32, "item_w"), ptr(flat.dest, _i32, "item_dest"),
+        call("gngf_ext3_vertex_grid_bwd_flat_owned" if owned else "gngf_vertex_grid_bwd_flat", ptr(flat.gi, _i32, "item_gi"),
+             ptr(flat.w, _f32, "item_w"), ptr(flat.dest, _i32, "item_dest"),
              flat.n, ptr(dG), ptr(dG64, _i64, "dG64"), plan.vtot, ptr(dtables, _f32, "dtables"), plan.Ls * T, F, stream_ptr())
         return
+    if owned:
+        raise ValueError("the row-owning vertex backward runs over a static item list only")
     if vert_idx is not None and order is not None:
         call("gngf_vertex_grid_bwd_sorted", *_tab(tables), ptr(vert_idx), ptr(vert_w), ptr(order, _i32, "order"), ptr(n_ls), ptr(dG),
              ptr(dG64, _i64, "dG64"), plan.vtot, ptr(dtables), ptr(dvw), plan.Ls, F, T, vert_idx.shape[1], vstride, vert_idx.shape[0],
@@ -1583,24 +1651,27 @@ class StepConfig:
     direct_bwd: str        # "bucketed_write" | "bucketed_or_atomics" (decided per call on the density) | "atomics" (dense_hash) | "none"
     exchange: bool         # a data-parallel exchange of the vertex-grid gradient is set up
     vertex_bwd_flat: bool = False      # vertex-table source: the backward of the vertex stage runs over the frozen table's static item list
+    owned_rows: bool = False           # ... and stores its rows into the model's step-to-step buffer: the clear covers the vertex grid only
 
     def signature(self):
         return (f"{self.source} L{self.staged}+{self.direct} bin={self.binning} vfwd={self.vertex_fwd} px={self.pixel} sink={self.grad_sink} "
                 f"dE={self.table_grad}/{self.clear} direct={self.direct_bwd}" + (" xchg" if self.exchange else "")
-                + (" vbwd=flat" if self.vertex_bwd_flat else ""))
+                + (" vbwd=flat" if self.vertex_bwd_flat else "") + (" rows=owned" if self.owned_rows else ""))
 
     def chain(self):
         """the signature without the level COUNTS (the same kernels run whether 4 or 16 levels are staged): the key the test
         coverage table of tests/test_step_config_cpu.py is written in (vertex_bwd_flat is not part of it either: the same chain
-        with another kernel for its last launch, selected by the caller's cached table and ops.VERTEX_BWD_FLAT)"""
+        with another kernel for its last launch, selected by the caller's cached table and ops.VERTEX_BWD_FLAT; nor is owned_rows,
+        the same again with that kernel storing its rows: ops.VERTEX_BWD_OWNED and the loop's dp.persist_ok)"""
         lv = ("tiled" if self.staged else "") + ("+" if self.staged and self.direct else "") + ("direct" if self.direct else "")
         return (f"{self.source} {lv} bin={self.binning} vfwd={self.vertex_fwd} px={self.pixel} sink={self.grad_sink} "
                 f"dE={self.table_grad}/{self.clear} direct={self.direct_bwd}" + (" xchg" if self.exchange else ""))
 
     @staticmethod
     def choose(plan, L, T, F, P, mode, fp32_tables, needs_grad, link_defer_zero, link_zero_hidden, exchange, persist_ok, persist_alloc_ok,
-               have_reserve_ws, flat_list=False):
+               have_reserve_ws, flat_list=False, owned_rows=False):
         """flat_list: the static item list of a frozen vertex table is at hand and no d w is wanted (see vertex_bwd_flat).
+        owned_rows: ... and the model's step-to-step buffer for that list is free (the loop opted in: see ops.VERTEX_BWD_OWNED).
         link_defer_zero / link_zero_hidden: the StepLink of the pass says a fused decoder kernel will clear the buffer it is left
         (zero_hidden: the one-launch training kernel, which clears for free).  persist_alloc_ok: the step-to-step buffer exists or may
         be allocated now (not inside a capture).  have_reserve_ws: the persistent counters of the two-launch binning exist."""
@@ -1640,8 +1711,10 @@ class StepConfig:
         vflat = bool(flat_list and mode != MODE_HASH)
         sink = "table_rows" if (mode == MODE_HASH and not exchange) else ("dG64" if use64 else "fp32_grid")
         if fused:
+            # (direct levels add to rows of their own: they keep the cleared allocation)
+            owned = bool(owned_rows and vflat and sink == "dG64" and not exchange and nd == 0)
             return StepConfig(src, plan.Ls, nd, "pipeline", "fused", "interleaved", sink, "block", "decoder" if link_defer_zero else "riders",
-                              "bucketed_or_atomics" if nd > 0 else "none", bool(exchange), vflat)
+                              "bucketed_or_atomics" if nd > 0 else "none", bool(exchange), vflat, owned)
         fresh = nd > 0 and mode == MODE_HASH and bucketed_plan(P, F, T, nd, True) is not None
         hidden = link_defer_zero and link_zero_hidden and L * T * F * 4 <= t.persistent_min_bytes
         persist = bool(t.persistent_table_grad and not hidden and mode == MODE_HASH and persist_ok and not exchange and (fresh or nd == 0)
@@ -1663,6 +1736,7 @@ class _BackwardBuffers:
     zbuf: object = None             # the buffer whose clear forward arranged: riders of the binning, or the decoder (link.zero_request)
     persist_cleared: object = None  # "persist": the buffer generation whose staged levels' rows the binning's riders cleared
     next_bin: object = None         # (workspace, gngf_bin_job, coordinates, BinPipeline): the next batch, binned by the backward's launch
+    owned: bool = False             # owned_rows: no dtables here — the backward takes the model's step-to-step buffer (_owned_peek)
 
 
 class EncodeFunction(torch.autograd.Function):
@@ -1692,12 +1766,17 @@ class EncodeFunction(torch.autograd.Function):
         tiled = plan.Ls > 0 and P > 0
         pws = _bin_workspace(dev, plan.ntiles, dp, kind="reserve") if (tiled and TUNING.fused_vertex_fwd) else None
         # ONE decision per pass (see StepConfig): which kernels, which buffers, who clears them
-        sc = ctx.step_config = StepConfig.choose(
+        choose_args = (
             plan, L, T, F, P, mode, tables.dtype == _f32, bool(ctx.needs_input_grad[3]),
             bool(link is not None and link.defer_zero), bool(link is not None and link.zero_hidden),
             bool(dp is not None and dp.exchange is not None), bool(dp is not None and dp.persist_ok and getattr(dp, "level_params", None)),
             bool(dp is not None and (getattr(dp, "persist_grad", None) is not None or not torch.cuda.is_current_stream_capturing())),
-            bool(pws is not None and pws.numel() >= 2 * plan.ntiles + 3), flat_list=ctx.flat is not None)
+            bool(pws is not None and pws.numel() >= 2 * plan.ntiles + 3))
+        # the step-to-step buffer of owned_rows is looked for (and made, outside a capture) only where the chain can use it
+        want_owned = bool(VERTEX_BWD_OWNED and ctx.flat is not None
+                          and StepConfig.choose(*choose_args, flat_list=True, owned_rows=True).owned_rows)
+        sc = ctx.step_config = StepConfig.choose(*choose_args, flat_list=ctx.flat is not None,
+                                                 owned_rows=want_owned and _owned_peek(dp, tables, ctx.flat) is not None)
         if dp is not None:
             dp.step_config = sc
         _trace("step_config", signature=sc.signature())
@@ -1717,7 +1796,12 @@ class EncodeFunction(torch.autograd.Function):
                 # adds to the table gradient itself
                 ng = 0 if sc.grad_sink == "table_rows" else ((plan.vtot * F + 2) * 2 if use64 else plan.vtot * F)
                 nt = tables.numel()
-                if fused:
+                if fused and sc.owned_rows:
+                    # the table gradient is the model's step-to-step buffer, whose rows the flat kernel stores: the clear (the
+                    # training decoder's, or the count launch's riders') covers the fixed-point vertex grid alone
+                    big = torch.empty(((ng + 3) & ~3,), dtype=_f32, device=dev)
+                    buf = _BackwardBuffers(big[:ng].view(_i64), None, zbuf=big, owned=True)
+                elif fused:
                     # ONE allocation [table gradient | vertex-grid gradient]: whoever clears the table gradient — the fused
                     # training decoder between its MFMAs, or rider workgroups of the count launch — clears both
                     big = torch.empty((nt + ((ng + 3) & ~3),), dtype=_f32, device=dev)
@@ -1831,7 +1915,14 @@ class EncodeFunction(torch.autograd.Function):
         if buf is not None and sc.table_grad == "persist":
             # staged levels' rows cleared (by this pass's forward, or now); the direct levels will be written
             dtables = _persistent_grad(dp, tables, plan, n_ls, buf.persist_cleared)
-        _trace("table_grad", source=("persist" if (dtables is not None and dp is not None and dtables is getattr(dp, "persist_grad", None))
+        # owned_rows: the step-to-step buffer, if the chain still is the one it was planned for and the buffer is still free (a
+        # second forward pass may have gone through a backward pass of its own since); else a zeroed allocation and the adding kernel
+        owned = bool(buf is not None and buf.owned and grad_sink == "dG64" and exchange is None and order is not None
+                     and ctx.flat is not None and VERTEX_BWD_FLAT and not ctx.needs_input_grad[5])
+        if owned:
+            dtables = _owned_peek(dp, tables, ctx.flat)
+            owned = dtables is not None
+        _trace("table_grad", source=("owned" if owned else "persist" if (dtables is not None and dp is not None and dtables is getattr(dp, "persist_grad", None))
                                      else ("forward_alloc" if dtables is not None else "zeroed_alloc")))
         # direct_bwd "bucketed_write": the direct levels of the buffer the forward pass left hold nothing yet (a zeroed one is not fresh)
         fresh_direct = dtables is not None and sc.direct_bwd == "bucketed_write"
@@ -1858,7 +1949,8 @@ class EncodeFunction(torch.autograd.Function):
             job_next = None
             if next_bin is not None and plan.interleaved(backward=True):
                 job_next = next_bin[1]
-            _pixel_bwd(plan, ws, n_ls, genc, dG, L, F, absmax, link, fuse, dG64, job_next)
+            _pixel_bwd(plan, ws, n_ls, genc, dG, L, F, absmax, link, fuse, dG64, job_next,
+                       clear=(dtables, ctx.flat.cross) if owned else None)
             if job_next is not None:
                 # the next batch is binned: its forward pass picks the workspace up if it is called with that very tensor
                 ws_next, _job, nx, pipe = next_bin
@@ -1888,7 +1980,8 @@ class EncodeFunction(torch.autograd.Function):
                 # (the frozen table's static item list, when the forward pass found one: the flat segmented reduction)
                 # (the index source is named only where the arguments do not already say it: the dense-where-it-fits source)
                 _vertex_bwd(plan, tables, vert_idx, vert_w, n_ls, vstride, dG, dtables, dvw, order, dG64 if direct64 else None,
-                            **({"mode": mode} if mode == MODE_DENSE_HASH else {}), **({"flat": ctx.flat} if ctx.flat is not None else {}))
+                            **({"mode": mode} if mode == MODE_DENSE_HASH else {}), **({"flat": ctx.flat} if ctx.flat is not None else {}),
+                            **({"owned": True} if owned else {}))
         else:
             dvw_t = None
         if plan.Ls < L:

@@ -14,12 +14,13 @@
 #define GNGF_EXT3_H_
 
 #include <stdint.h>
+#include "gngf.h"      /* gngf_bin_job */
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define GNGF_EXT3_VERSION 1
+#define GNGF_EXT3_VERSION 2
 
 int gngf_ext3_version(void);
 
@@ -64,6 +65,45 @@ int gngf_ext3_query_grid(const float* grid, const int32_t* n_ls, const int32_t* 
                          const float* W0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
                          int L, int F, int out_dim, int leaky,
                          const float* xy, int64_t P, float* rgb, int32_t* img, void* stream);
+
+/*
+ * (version 2) The flat vertex backward that OWNS its rows (csrc/vertex_flat_owned.hip): the arguments, the list, the item values,
+ * the checks and the launch shape (ceil(N / 1024) workgroups of 256 threads, 4 items each) of gngf_vertex_grid_bwd_flat
+ * (include/gngf.h) — but dtables is WRITTEN and added to, not only accumulated into, so it need not be zero:
+ *   a run of equal item_dest that lies wholly inside one workgroup's 1024 items: its row (F floats) is STORED, 0.f + sum — a zero
+ *     sum too (the row may hold an older value), and a -0.0 sum as +0.0, which is what adding it to a zeroed row leaves;
+ *   a run that enters or leaves a workgroup (the workgroup reads item_dest[first - 1] and item_dest[end] to tell): each part is
+ *     ADDED with a float atomic, zero sums skipped — the caller zeroes these rows before the launch (at most one per boundary
+ *     between two workgroups; gngf_ext3_encode_tiled_bwd_clear_rows does it inside the launch that precedes this one);
+ *   a row no item names is neither read nor written.
+ * With those rows zeroed the result equals gngf_vertex_grid_bwd_flat's on a zeroed buffer, bit for bit wherever a run has at most
+ * two parts (same partial sums, combined in the same order; a two-term add commutes).  No workgroup waits for another.
+ * Rejected: what gngf_vertex_grid_bwd_flat rejects; dtables not aligned to min(4 F, 16) bytes.
+ */
+int gngf_ext3_vertex_grid_bwd_flat_owned(const int32_t* item_gi, const float* item_w, const int32_t* item_dest, int64_t N,
+                                         const float* dG, const void* dG64, int64_t vtot, float* dtables, int64_t rows, int F,
+                                         void* stream);
+
+/*
+ * (version 2) gngf_encode_tiled_bwd (include/gngf.h: same arguments, same meaning, same launches) with a row-clear rider:
+ * a few more workgroups of the level-interleaved kernel's launch (one row per thread) store zeros to the F floats at
+ * clear_base + F * clear_rows[i], i < n_clear_rows (a negative row number is skipped; the caller checks the upper range).  The
+ * launch reads and writes clear_base nowhere else; the rows are clear when the next launch on the stream starts.
+ * n_clear_rows == 0: exactly gngf_encode_tiled_bwd (clear_base / clear_rows are not looked at).
+ * Rejected: what gngf_encode_tiled_bwd rejects; n_clear_rows < 0 or > 2^24; with n_clear_rows > 0: a NULL clear_base or clear_rows,
+ *   max_items == 0, or a shape the level-interleaved backward kernel does not take (gngf_tiled_interleaved_applies).
+ */
+int gngf_ext3_encode_tiled_bwd_clear_rows(const float* sorted, const int32_t* items, const int32_t* n_items, int max_items,
+                          const int32_t* tile_item_base, const int32_t* tile_level_off, const int32_t* n_ls,
+                          const int32_t* n_ls_host, const float* genc, const float* genc_absmax, int absmax_count,
+                          int absmax_stride, float* dG, float* partials, int L, int Ls, int F, int tile_shift,
+                          int lds_bytes, int chunk, const float* ride_slabs, float* ride_dW0, float* ride_db0,
+                          float* ride_dW1, float* ride_db1, float* ride_dW2, float* ride_db2, int64_t ride_P,
+                          int ride_in_dim, int ride_out_dim, const float* gloss_promised, const float* gloss_arrived,
+                          const float* mse_pred, const float* mse_label,
+                          float* mse_loss, float* mse_workspace, int64_t mse_n, float* hash_dtables, int64_t hash_T,
+                          void* dG64, int log2_pixels, const gngf_bin_job* next_bin,
+                          float* clear_base, const int32_t* clear_rows, int n_clear_rows, void* stream);
 
 #ifdef __cplusplus
 }
