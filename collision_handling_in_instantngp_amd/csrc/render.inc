@@ -1,6 +1,7 @@
-// Forward-only render of a pixel lattice in ONE launch (included at the end of decoder.hip, and by render_score.hip for the
-// scoring forms: it needs decoder_common.inc — stage_raw / raw_offsets, crow / kmapC, the MFMA macro — and repeats the 4x4x1 output
-// layer of decoder_fwd_kernel with its sigmoid).
+// Forward-only render of a pixel lattice in ONE launch (included at the end of decoder.hip, and by render_score.hip and
+// render_query.hip for the scoring and query forms: it needs decoder_common.inc — stage_raw / raw_offsets, crow / kmapC, the MFMA
+// macro — and repeats the 4x4x1 output layer of decoder_fwd_kernel with its sigmoid).  Below the kernel: the host side every
+// entry point shares — the model checks, the picker, the launch — and decoder.hip's own two entry points.
 //
 // decoder_fwd_kernel with its input produced in place: a lane owns one pixel of the lattice (col = lane & 31 of the transposed
 // products), computes the pixel's coordinate from its row and column — ((float)(r0 + r) / denom, (float)(c0 + c) / denom), one
@@ -449,67 +450,116 @@ render_kernel(const RenderArgs a, const typename RenderSrcArgs<SRC>::type ga) {
 }
 #undef RENDER_F
 
-#ifndef GNGF_RENDER_KERNELS_ONLY        // (render_score.hip takes the kernel and brings its own entry points)
+// ---- Host side, shared by the entry points of decoder.hip (below), render_score.hip and render_query.hip.  An entry point reads:
+// its own sink and walk checks | the model (render_table_model / render_grid_model) | the pick | the launch.  A unit emits
+// the kernels of the sources it names in its picks, and no others.
 
-using RenderKern = void (*)(const RenderArgs, const RenderNoGrid);
-template <int KIN, typename TT> static RenderKern render_pick(bool leaky, bool exact, bool vt) {
-  if (leaky) {
-    if (exact) return vt ? render_kernel<KIN, true, true, kSrcTable, TT> : render_kernel<KIN, true, true, kSrcHash, TT>;
-    return vt ? render_kernel<KIN, true, false, kSrcTable, TT> : render_kernel<KIN, true, false, kSrcHash, TT>;
+constexpr int kRenderMaxGrid = 256;                       // one persistent workgroup per CU: the largest grid of every form
+
+template <int SRC> using RenderKern = void (*)(const RenderArgs, const typename RenderSrcArgs<SRC>::type);
+// leaky x (32 | 64 features wide) x (exactly that wide | narrower) of one source and table type
+template <int SRC, typename TT> static RenderKern<SRC> render_pick(int in_dim, bool leaky) {
+  if (in_dim == 32) return leaky ? render_kernel<32, true, true, SRC, TT> : render_kernel<32, false, true, SRC, TT>;
+  if (in_dim < 32) return leaky ? render_kernel<32, true, false, SRC, TT> : render_kernel<32, false, false, SRC, TT>;
+  if (in_dim == 64) return leaky ? render_kernel<64, true, true, SRC, TT> : render_kernel<64, false, true, SRC, TT>;
+  return leaky ? render_kernel<64, true, false, SRC, TT> : render_kernel<64, false, false, SRC, TT>;
+}
+template <int SRC> static RenderKern<SRC> render_pick(bool f16, int in_dim, bool leaky) {
+  return f16 ? render_pick<SRC, __half>(in_dim, leaky) : render_pick<SRC, float>(in_dim, leaky);
+}
+// the three table sources of one family (BASE = 0: storing, kSrcScore, kSrcQuery) by the model's mode and table type
+template <int BASE> static RenderKern<BASE + kSrcHash> render_pick_mode(int mode, int feat_dtype, int in_dim, bool leaky) {
+  const bool f16 = feat_dtype == GNGF_FEAT_F16;
+  return mode == GNGF_MODE_DENSE_HASH     ? render_pick<BASE + kSrcDenseHash>(f16, in_dim, leaky)
+         : mode == GNGF_MODE_VERTEX_TABLE ? render_pick<BASE + kSrcTable>(f16, in_dim, leaky)
+                                          : render_pick<BASE + kSrcHash>(f16, in_dim, leaky);
+}
+
+// what both models share: the level resolutions, the decoder and the widths.  false: refused
+static bool render_decoder(RenderArgs& a, const int32_t* n_ls, const float* W0, const float* b0, const float* W1, const float* b1,
+                           const float* W2, const float* b2, int L, int F, int out_dim) {
+  if (!(L > 0 && L <= GNGF_MAX_LEVELS && (F == 1 || F == 2 || F == 4) && L * F <= 64 && out_dim > 0 && out_dim <= 4)) return false;
+  if (!(n_ls && W0 && b0 && W1 && b1 && W2 && b2)) return false;
+  a.n_ls = n_ls; a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2;
+  a.L = L; a.F = F; a.out_dim = out_dim;
+  return true;
+}
+
+// The table-sourced model (hash, vertex table, dense-where-it-fits): checks it and fills the model part of `a` — everything
+// but the sink (rgb, img) and the walk (rows, cols, r0, c0, denom).  false: refused
+static bool render_table_model(RenderArgs& a, const void* tables, int feat_dtype, const int32_t* vert_idx, const float* vert_w,
+                               const int32_t* n_ls, const float* W0, const float* b0, const float* W1, const float* b1,
+                               const float* W2, const float* b2, int L, int F, int64_t T, int K, int mode, int vstride, int64_t NV,
+                               int out_dim) {
+  if (!render_decoder(a, n_ls, W0, b0, W1, b1, W2, b2, L, F, out_dim) || T <= 0) return false;
+  if (mode != GNGF_MODE_HASH && mode != GNGF_MODE_VERTEX_TABLE && mode != GNGF_MODE_DENSE_HASH) return false;
+  if (feat_dtype != GNGF_FEAT_F32 && feat_dtype != GNGF_FEAT_F16) return false;
+  if (!tables || (reinterpret_cast<uintptr_t>(tables) & 15) != 0) return false;
+  const bool vt = mode == GNGF_MODE_VERTEX_TABLE;
+  if (vt && !(vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0 && NV * K < ((int64_t)1 << 31))) return false;
+  a.tables = tables; a.vert_idx = vert_idx; a.vert_w = vert_w;
+  a.T = T; a.K = vt ? K : 0; a.vstride = vt ? vstride : 0; a.NV = vt ? NV : 0;
+  a.pow2 = (T & (T - 1)) == 0;
+  return true;
+}
+
+// The grid-sourced model (a baked vertex grid): as render_table_model, and goff[l] = the first row of level l's grid, from
+// the host mirror of the resolutions.  false: refused
+static bool render_grid_model(RenderArgs& a, int64_t (&goff)[GNGF_MAX_LEVELS], const float* grid, const int32_t* n_ls,
+                              const int32_t* n_ls_host, const float* W0, const float* b0, const float* W1, const float* b1,
+                              const float* W2, const float* b2, int L, int F, int out_dim) {
+  if (!render_decoder(a, n_ls, W0, b0, W1, b1, W2, b2, L, F, out_dim)) return false;
+  if (!grid || !n_ls_host || (reinterpret_cast<uintptr_t>(grid) & 15) != 0) return false;
+  int64_t vtot = 0;
+  for (int l = 0; l < GNGF_MAX_LEVELS; ++l) {
+    goff[l] = vtot;
+    if (l < L) {
+      if (n_ls_host[l] < 0) return false;
+      vtot += (int64_t)(n_ls_host[l] + 2) * (n_ls_host[l] + 2);
+    }
   }
-  if (exact) return vt ? render_kernel<KIN, false, true, kSrcTable, TT> : render_kernel<KIN, false, true, kSrcHash, TT>;
-  return vt ? render_kernel<KIN, false, false, kSrcTable, TT> : render_kernel<KIN, false, false, kSrcHash, TT>;
-}
-template <int KIN, typename TT> static RenderKern render_pick_dense_hash(bool leaky, bool exact) {
-  if (leaky) return exact ? render_kernel<KIN, true, true, kSrcDenseHash, TT> : render_kernel<KIN, true, false, kSrcDenseHash, TT>;
-  return exact ? render_kernel<KIN, false, true, kSrcDenseHash, TT> : render_kernel<KIN, false, false, kSrcDenseHash, TT>;
-}
-using RenderGridKern = void (*)(const RenderArgs, const RenderGridArgs);
-template <int KIN> static RenderGridKern render_pick_grid(bool leaky, bool exact) {
-  if (leaky) return exact ? render_kernel<KIN, true, true, kSrcGrid, float> : render_kernel<KIN, true, false, kSrcGrid, float>;
-  return exact ? render_kernel<KIN, false, true, kSrcGrid, float> : render_kernel<KIN, false, false, kSrcGrid, float>;
+  a.tables = nullptr; a.vert_idx = nullptr; a.vert_w = nullptr;
+  a.T = 0; a.K = 0; a.vstride = 0; a.NV = 0; a.pow2 = false;
+  return true;
 }
 
-#endif  // GNGF_RENDER_KERNELS_ONLY
+// the blocks the kernel walks on a rows x cols lattice
+static int64_t render_blocks(int64_t rows, int64_t cols) {
+  return ((cols + kRenderCols - 1) / kRenderCols) * ((rows + kRenderRows - 1) / kRenderRows);
+}
+
+// One launch over nblocks blocks; returns the number of workgroups (the scoring form's finish kernel sums that many partials)
+template <typename GA>
+static int render_launch(void (*fn)(const RenderArgs, const GA), const RenderArgs& a, const GA& ga, int64_t nblocks, hipStream_t s) {
+  const int nwg = (int)(nblocks < kRenderMaxGrid ? nblocks : kRenderMaxGrid);
+  const size_t smem = sizeof(float) * (size_t)raw_offsets(a.L * a.F).total;
+  fn<<<dim3((unsigned)nwg), dim3(kDecThreads), smem, s>>>(a, ga);
+  return nwg;
+}
+
+// the sink and the walk of the two lattice forms (gngf_render, gngf_render_grid).  false: refused
+static bool render_lattice_walk(RenderArgs& a, float* rgb, int32_t* img, int64_t rows, int64_t cols, int64_t r0, int64_t c0,
+                                float denom) {
+  constexpr int64_t kExact = (int64_t)1 << 24;            // integers up to here are exact in fp32
+  if (!(rows >= 1 && cols >= 1 && denom > 0.f && r0 >= -kExact && c0 >= -kExact && r0 + rows <= kExact && c0 + cols <= kExact)) return false;
+  if (!(rgb || img)) return false;
+  a.rgb = rgb; a.img = img; a.rows = rows; a.cols = cols; a.r0 = r0; a.c0 = c0; a.denom = denom;
+  return true;
+}
 
 }  // namespace gngf
 
-#ifndef GNGF_RENDER_KERNELS_ONLY
+#ifndef GNGF_RENDER_KERNELS_ONLY        // (render_score.hip and render_query.hip bring their own entry points)
 // rgb (rows cols, out_dim) fp32 and / or img (same shape) int32 = (int)(rgb * 255.0f) of the model on the lattice
 // ((r0 + r) / denom, (c0 + c) / denom), r < rows, c < cols, row-major.  See include/gngf.h.
 extern "C" int gngf_render(const void* tables, int feat_dtype, const int32_t* vert_idx, const float* vert_w, const int32_t* n_ls,
                            const float* W0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
                            float* rgb, int32_t* img, int64_t rows, int64_t cols, int64_t r0, int64_t c0, float denom,
                            int L, int F, int64_t T, int K, int mode, int vstride, int64_t NV, int out_dim, int leaky, void* stream) {
-  constexpr int64_t kExact = (int64_t)1 << 24;            // integers up to here are exact in fp32
-  GNGF_CHECK_ARG(L > 0 && L <= GNGF_MAX_LEVELS && (F == 1 || F == 2 || F == 4) && L * F <= 64 && T > 0);
-  GNGF_CHECK_ARG(out_dim > 0 && out_dim <= 4);
-  GNGF_CHECK_ARG(rows >= 1 && cols >= 1 && denom > 0.f && r0 >= -kExact && c0 >= -kExact && r0 + rows <= kExact && c0 + cols <= kExact);
-  GNGF_CHECK_ARG(mode == GNGF_MODE_HASH || mode == GNGF_MODE_VERTEX_TABLE || mode == GNGF_MODE_DENSE_HASH);
-  GNGF_CHECK_ARG(feat_dtype == GNGF_FEAT_F32 || feat_dtype == GNGF_FEAT_F16);
-  GNGF_CHECK_ARG(tables && n_ls && W0 && b0 && W1 && b1 && W2 && b2 && (rgb || img));
-  GNGF_CHECK_ARG((reinterpret_cast<uintptr_t>(tables) & 15) == 0);
-  const bool vt = mode == GNGF_MODE_VERTEX_TABLE;
-  if (vt) GNGF_CHECK_ARG(vert_idx && vert_w && K > 0 && K <= GNGF_MAX_TOPK_WIDE && vstride > 0 && NV > 0 && NV * K < ((int64_t)1 << 31));
   RenderArgs a;
-  a.tables = tables; a.vert_idx = vert_idx; a.vert_w = vert_w; a.n_ls = n_ls;
-  a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2;
-  a.rgb = rgb; a.img = img;
-  a.rows = rows; a.cols = cols; a.r0 = r0; a.c0 = c0; a.denom = denom;
-  a.L = L; a.F = F; a.T = T; a.K = vt ? K : 0; a.vstride = vt ? vstride : 0; a.NV = vt ? NV : 0;
-  a.out_dim = out_dim; a.pow2 = (T & (T - 1)) == 0;
-  const int in_dim = L * F;
-  const int64_t nblocks = ((cols + kRenderCols - 1) / kRenderCols) * ((rows + kRenderRows - 1) / kRenderRows);
-  const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);      // one persistent workgroup per CU
-  const size_t smem = sizeof(float) * (size_t)raw_offsets(in_dim).total;
-  const bool f16 = feat_dtype == GNGF_FEAT_F16;
-  RenderKern fn;
-  if (mode == GNGF_MODE_DENSE_HASH) {
-    if (in_dim <= 32) fn = f16 ? render_pick_dense_hash<32, __half>(leaky != 0, in_dim == 32) : render_pick_dense_hash<32, float>(leaky != 0, in_dim == 32);
-    else fn = f16 ? render_pick_dense_hash<64, __half>(leaky != 0, in_dim == 64) : render_pick_dense_hash<64, float>(leaky != 0, in_dim == 64);
-  } else if (in_dim <= 32) fn = f16 ? render_pick<32, __half>(leaky != 0, in_dim == 32, vt) : render_pick<32, float>(leaky != 0, in_dim == 32, vt);
-  else fn = f16 ? render_pick<64, __half>(leaky != 0, in_dim == 64, vt) : render_pick<64, float>(leaky != 0, in_dim == 64, vt);
-  fn<<<dim3(grid), dim3(kDecThreads), smem, as_stream(stream)>>>(a, RenderNoGrid{});
+  GNGF_CHECK_ARG(render_lattice_walk(a, rgb, img, rows, cols, r0, c0, denom));
+  GNGF_CHECK_ARG(render_table_model(a, tables, feat_dtype, vert_idx, vert_w, n_ls, W0, b0, W1, b1, W2, b2, L, F, T, K, mode, vstride, NV, out_dim));
+  render_launch(render_pick_mode<0>(mode, feat_dtype, L * F, leaky != 0), a, RenderNoGrid{}, render_blocks(rows, cols), as_stream(stream));
   GNGF_RETURN_LAUNCH();
 }
 
@@ -518,35 +568,13 @@ extern "C" int gngf_render_grid(const float* grid, const int32_t* n_ls, const in
                                 const float* W0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
                                 float* rgb, int32_t* img, int64_t rows, int64_t cols, int64_t r0, int64_t c0, float denom,
                                 int L, int F, int out_dim, int leaky, void* stream) {
-  constexpr int64_t kExact = (int64_t)1 << 24;
-  GNGF_CHECK_ARG(L > 0 && L <= GNGF_MAX_LEVELS && (F == 1 || F == 2 || F == 4) && L * F <= 64);
-  GNGF_CHECK_ARG(out_dim > 0 && out_dim <= 4);
-  GNGF_CHECK_ARG(rows >= 1 && cols >= 1 && denom > 0.f && r0 >= -kExact && c0 >= -kExact && r0 + rows <= kExact && c0 + cols <= kExact);
-  GNGF_CHECK_ARG(grid && n_ls && n_ls_host && W0 && b0 && W1 && b1 && W2 && b2 && (rgb || img));
-  GNGF_CHECK_ARG((reinterpret_cast<uintptr_t>(grid) & 15) == 0);
   RenderArgs a;
-  a.tables = nullptr; a.vert_idx = nullptr; a.vert_w = nullptr; a.n_ls = n_ls;
-  a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2;
-  a.rgb = rgb; a.img = img;
-  a.rows = rows; a.cols = cols; a.r0 = r0; a.c0 = c0; a.denom = denom;
-  a.L = L; a.F = F; a.T = 0; a.K = 0; a.vstride = 0; a.NV = 0;
-  a.out_dim = out_dim; a.pow2 = false;
   RenderGridArgs ga;
   ga.grid = grid;
-  int64_t vtot = 0;
-  for (int l = 0; l < GNGF_MAX_LEVELS; ++l) {
-    ga.goff[l] = vtot;
-    if (l < L) {
-      GNGF_CHECK_ARG(n_ls_host[l] >= 0);
-      vtot += (int64_t)(n_ls_host[l] + 2) * (n_ls_host[l] + 2);
-    }
-  }
-  const int in_dim = L * F;
-  const int64_t nblocks = ((cols + kRenderCols - 1) / kRenderCols) * ((rows + kRenderRows - 1) / kRenderRows);
-  const unsigned nwg = (unsigned)(nblocks < 256 ? nblocks : 256);       // one persistent workgroup per CU
-  const size_t smem = sizeof(float) * (size_t)raw_offsets(in_dim).total;
-  const RenderGridKern fn = in_dim <= 32 ? render_pick_grid<32>(leaky != 0, in_dim == 32) : render_pick_grid<64>(leaky != 0, in_dim == 64);
-  fn<<<dim3(nwg), dim3(kDecThreads), smem, as_stream(stream)>>>(a, ga);
+  GNGF_CHECK_ARG(render_lattice_walk(a, rgb, img, rows, cols, r0, c0, denom));
+  GNGF_CHECK_ARG(render_grid_model(a, ga.goff, grid, n_ls, n_ls_host, W0, b0, W1, b1, W2, b2, L, F, out_dim));
+  render_launch(render_pick<kSrcGrid, float>(L * F, leaky != 0), a, ga, render_blocks(rows, cols), as_stream(stream));
   GNGF_RETURN_LAUNCH();
 }
 #endif  // GNGF_RENDER_KERNELS_ONLY
+

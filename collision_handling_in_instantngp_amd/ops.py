@@ -2178,6 +2178,69 @@ def sample_pixels(image, seed, draw, xy, target, *, denom, continuous):
     call("gngf_ext_sample_pixels", *args)
 
 
+# The forward-only entry points (render_lattice, render_score, query_points; render_grid, query_grid_points) share their model
+# arguments: one helper per kind of model checks them and returns the runs of arguments the C call takes.
+
+def _decoder_model(who, L, F, n_ls, decoder_params):
+    """(C, the pointer run n_ls, W0 .. b2) of a decoder (L F -> 64 -> 64 -> C) over L levels — or ValueError naming `who`"""
+    W0, _b0, W1, _b1, W2, _b2 = decoder_params
+    if tuple(W0.shape) != (64, L * F) or tuple(W1.shape) != (64, 64) or W2.shape[1] != 64:
+        raise ValueError(f"{who}: decoder ({L * F} -> 64 -> 64 -> C) expected, got {tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
+    if n_ls.numel() != L:
+        raise ValueError(f"n_ls holds {n_ls.numel()} resolutions for {L} levels")
+    return W2.shape[0], (ptr(n_ls, _i32, "n_ls"),
+                         *(ptr(t, _f32, name) for t, name in zip(decoder_params, ("W0", "b0", "W1", "b1", "W2", "b2"))))
+
+
+def _table_model(who, tables, n_ls, decoder_params, vert_idx, vert_w, vstride, leaky, mode):
+    """The table-sourced model of a forward-only call, checked: (C, pointers, scalars) with the runs of the C signatures —
+    pointers = (tables, feat_dtype, vert_idx, vert_w, n_ls, W0 .. b2), scalars = (L, F, T, K, mode, vstride, NV, C, leaky).
+    gngf_render places its outputs and lattice between the two; the ext2 and ext3 calls place theirs behind both."""
+    L, T, F = tables.shape
+    vt = vert_idx is not None
+    K = check_topk(vert_idx.shape[1]) if vt else 0
+    NV = int(vert_idx.shape[0]) if vt else 0
+    if vt and tuple(vert_w.shape) != (NV, K):
+        raise ValueError(f"vert_w must be (NV, K) = ({NV}, {K}), got {tuple(vert_w.shape)}")
+    C, decoder = _decoder_model(who, L, F, n_ls, decoder_params)
+    return (C, (*_tab(tables), ptr(vert_idx, _i32, "vert_idx"), ptr(vert_w, _f32, "vert_w"), *decoder),
+            (L, F, T, K, index_source(vert_idx, mode), int(vstride), NV, C, int(bool(leaky))))
+
+
+def baked_level_offsets(n_ls_host):
+    """(offsets, vtot) of a baked grid: level l's (N_l + 2) x (N_l + 2) vertices are rows offsets[l] + gy (N_l + 2) + gx of the
+    (vtot, F) grid, offsets[l] = sum_{j<l} (N_j + 2)^2 (include/gngf.h: gngf_vertex_grid_fwd).  A coordinate in [0, 1] reaches
+    corners 0 .. floor(N_l) + 1 = N_l + 1 per axis: all inside the level."""
+    offsets, vtot = [], 0
+    for n in n_ls_host:
+        offsets.append(vtot)
+        vtot += (int(n) + 2) ** 2
+    return offsets, vtot
+
+
+def _grid_model(who, grid, n_ls, n_ls_host, decoder_params, leaky):
+    """The grid-sourced model (a baked vertex grid) of a forward-only call, checked: (C, pointers, scalars) with
+    pointers = (grid, n_ls, n_ls_host, W0 .. b2), scalars = (L, F, C, leaky); both C calls place the rest between the two."""
+    L = len(n_ls_host)
+    vtot = baked_level_offsets(n_ls_host)[1]
+    if grid.dim() != 2 or grid.shape[0] != vtot:
+        raise ValueError(f"{who}: grid must be ({vtot}, F) for these resolutions, got {tuple(grid.shape)}")
+    F = int(grid.shape[1])
+    C, (n_ls_ptr, *decoder) = _decoder_model(who, L, F, n_ls, decoder_params)
+    return (C, (ptr(grid, _f32, "grid"), n_ls_ptr, (_ct.c_int32 * L)(*[int(n) for n in n_ls_host]), *decoder),
+            (L, F, C, int(bool(leaky))))
+
+
+def _lattice_sink(who, rows, cols, C, out_rgb, out_image):
+    """the output pointers of a lattice form, after their checks: at least one, each of rows cols C elements"""
+    if out_rgb is None and out_image is None:
+        raise ValueError(f"{who}: pass out_rgb, out_image or both")
+    for name, t in (("out_rgb", out_rgb), ("out_image", out_image)):
+        if t is not None and t.numel() != rows * cols * C:
+            raise ValueError(f"{name} holds {t.numel()} elements for a {rows} x {cols} x {C} render")
+    return ptr(out_rgb, _f32, "out_rgb"), ptr(out_image, _i32, "out_image")
+
+
 def render_lattice(tables, n_ls, decoder_params, rows, cols, denom, origin=(0, 0), *, vert_idx=None, vert_w=None, vstride=0,
                    leaky=False, out_rgb=None, out_image=None, mode=None):
     """The model on the lattice ((r0 + r) / denom, (c0 + c) / denom), r < rows, c < cols, in one forward-only launch
@@ -2186,28 +2249,9 @@ def render_lattice(tables, n_ls, decoder_params, rows, cols, denom, origin=(0, 0
     spatial hash — or, with mode=MODE_DENSE_HASH, the dense-where-it-fits source (index_source).
     out_rgb (rows cols, C) fp32 and / or out_image (same shape) int32 are written; at least one is needed.
     No autograd, no workspace, no allocation, no synchronisation — and no StepConfig: this is not a step of training."""
-    L, T, F = tables.shape
-    W0, b0, W1, b1, W2, b2 = decoder_params
-    C = W2.shape[0]
-    if tuple(W0.shape) != (64, L * F) or tuple(W1.shape) != (64, 64) or W2.shape[1] != 64:
-        raise ValueError(f"render_lattice: decoder ({L * F} -> 64 -> 64 -> C) expected, got {tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
-    if n_ls.numel() != L:
-        raise ValueError(f"n_ls holds {n_ls.numel()} resolutions for {L} levels")
-    if out_rgb is None and out_image is None:
-        raise ValueError("render_lattice: pass out_rgb, out_image or both")
-    for name, t in (("out_rgb", out_rgb), ("out_image", out_image)):
-        if t is not None and t.numel() != rows * cols * C:
-            raise ValueError(f"{name} holds {t.numel()} elements for a {rows} x {cols} x {C} render")
-    vt = vert_idx is not None
-    K = check_topk(vert_idx.shape[1]) if vt else 0
-    tp, code = _tab(tables)
-    NV = int(vert_idx.shape[0]) if vt else 0
-    if vt and tuple(vert_w.shape) != (NV, K):
-        raise ValueError(f"vert_w must be (NV, K) = ({NV}, {K}), got {tuple(vert_w.shape)}")
-    call("gngf_render", tp, code, ptr(vert_idx, _i32, "vert_idx"), ptr(vert_w, _f32, "vert_w"), ptr(n_ls, _i32, "n_ls"),
-         ptr(W0, _f32, "W0"), ptr(b0, _f32, "b0"), ptr(W1, _f32, "W1"), ptr(b1, _f32, "b1"), ptr(W2, _f32, "W2"), ptr(b2, _f32, "b2"),
-         ptr(out_rgb, _f32, "out_rgb"), ptr(out_image, _i32, "out_image"), int(rows), int(cols), int(origin[0]), int(origin[1]),
-         float(denom), L, F, T, K, index_source(vert_idx, mode), int(vstride), NV, C, int(bool(leaky)), stream_ptr())
+    C, pointers, scalars = _table_model("render_lattice", tables, n_ls, decoder_params, vert_idx, vert_w, vstride, leaky, mode)
+    call("gngf_render", *pointers, *_lattice_sink("render_lattice", rows, cols, C, out_rgb, out_image), int(rows), int(cols),
+         int(origin[0]), int(origin[1]), float(denom), *scalars, stream_ptr())
 
 
 def render_score_workspace(device):
@@ -2222,13 +2266,7 @@ def render_score(tables, n_ls, decoder_params, image, *, denom, step=1, sums, wo
     (csrc/render.inc: the scoring form; include/gngf_ext2.h has the contract to the bit).  The model arguments are
     render_lattice's.  workspace: render_score_workspace(device).  Everything is checked here, before any device work; no
     allocation, no synchronisation: capturable.  Returns sums."""
-    L, T, F = tables.shape
-    W0, b0, W1, b1, W2, b2 = decoder_params
-    C = W2.shape[0]
-    if tuple(W0.shape) != (64, L * F) or tuple(W1.shape) != (64, 64) or W2.shape[1] != 64:
-        raise ValueError(f"render_score: decoder ({L * F} -> 64 -> 64 -> C) expected, got {tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
-    if n_ls.numel() != L:
-        raise ValueError(f"n_ls holds {n_ls.numel()} resolutions for {L} levels")
+    C, pointers, scalars = _table_model("render_score", tables, n_ls, decoder_params, vert_idx, vert_w, vstride, leaky, mode)
     if image.dim() != 3:
         raise ValueError(f"image must be (h, w, C), got {tuple(image.shape)}")
     h, w, Ci = (int(s) for s in image.shape)
@@ -2244,22 +2282,9 @@ def render_score(tables, n_ls, decoder_params, image, *, denom, step=1, sums, wo
         raise ValueError(f"denom must be > 0, got {denom}")
     if sums.numel() != 2 or workspace.numel() < query("gngf_ext2_render_score_workspace_words"):
         raise ValueError("sums must hold 2 words and workspace gngf_ext2_render_score_workspace_words() words")
-    vt = vert_idx is not None
-    K = check_topk(vert_idx.shape[1]) if vt else 0
-    tp, code = _tab(tables)
-    NV = int(vert_idx.shape[0]) if vt else 0
-    if vt and tuple(vert_w.shape) != (NV, K):
-        raise ValueError(f"vert_w must be (NV, K) = ({NV}, {K}), got {tuple(vert_w.shape)}")
-    call("gngf_ext2_render_score", tp, code, ptr(vert_idx, _i32, "vert_idx"), ptr(vert_w, _f32, "vert_w"), ptr(n_ls, _i32, "n_ls"),
-         ptr(W0, _f32, "W0"), ptr(b0, _f32, "b0"), ptr(W1, _f32, "W1"), ptr(b1, _f32, "b1"), ptr(W2, _f32, "W2"), ptr(b2, _f32, "b2"),
-         L, F, T, K, index_source(vert_idx, mode), int(vstride), NV, C, int(bool(leaky)),
-         ptr(image, torch.uint8, "image"), h, w, C, denom, min(step, 1 << 62), ptr(sums, _i64, "sums"),
-         ptr(workspace, _i64, "workspace"), stream_ptr())
+    call("gngf_ext2_render_score", *pointers, *scalars, ptr(image, torch.uint8, "image"), h, w, C, denom, min(step, 1 << 62),
+         ptr(sums, _i64, "sums"), ptr(workspace, _i64, "workspace"), stream_ptr())
     return sums
-
-
-def _grid_vertices(n_ls_host):
-    return sum((int(n) + 2) ** 2 for n in n_ls_host)
 
 
 def bake_vertex_grid(tables, n_ls, n_ls_host, vert_idx, vert_w, vstride, NV, F, T, K, out=None, mode=None):
@@ -2277,7 +2302,7 @@ def bake_vertex_grid(tables, n_ls, n_ls_host, vert_idx, vert_w, vstride, NV, F, 
     K = check_topk(K) if vt else 0
     if vt and (tuple(vert_idx.shape) != (NV, K) or tuple(vert_w.shape) != (NV, K)):
         raise ValueError(f"vert_idx and vert_w must be (NV, K) = ({NV}, {K}), got {tuple(vert_idx.shape)}, {tuple(vert_w.shape)}")
-    vtot = _grid_vertices(n_ls_host)
+    vtot = baked_level_offsets(n_ls_host)[1]
     if out is None:
         out = torch.empty((vtot, F), dtype=_f32, device=tables.device)
     elif out.numel() != vtot * F:
@@ -2293,26 +2318,9 @@ def render_grid(grid, n_ls, n_ls_host, decoder_params, rows, cols, denom, origin
     """render_lattice from a baked vertex grid (bake_vertex_grid's layout; csrc/render.inc: gngf_render_grid): the four corner
     rows of a level are dense loads from grid (vtot, F) fp32 — no tables, no vert_idx / vert_w, no hash.  Corners are clamped
     to the level's grid, so no coordinate faults; only coordinates in [0, 1]^2 give the model's values."""
-    L = len(n_ls_host)
-    W0, b0, W1, b1, W2, b2 = decoder_params
-    C = W2.shape[0]
-    vtot = _grid_vertices(n_ls_host)
-    if grid.dim() != 2 or grid.shape[0] != vtot:
-        raise ValueError(f"render_grid: grid must be ({vtot}, F) for these resolutions, got {tuple(grid.shape)}")
-    F = int(grid.shape[1])
-    if tuple(W0.shape) != (64, L * F) or tuple(W1.shape) != (64, 64) or W2.shape[1] != 64:
-        raise ValueError(f"render_grid: decoder ({L * F} -> 64 -> 64 -> C) expected, got {tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
-    if n_ls.numel() != L:
-        raise ValueError(f"n_ls holds {n_ls.numel()} resolutions for {L} levels")
-    if out_rgb is None and out_image is None:
-        raise ValueError("render_grid: pass out_rgb, out_image or both")
-    for name, t in (("out_rgb", out_rgb), ("out_image", out_image)):
-        if t is not None and t.numel() != rows * cols * C:
-            raise ValueError(f"{name} holds {t.numel()} elements for a {rows} x {cols} x {C} render")
-    call("gngf_render_grid", ptr(grid, _f32, "grid"), ptr(n_ls, _i32, "n_ls"), (_ct.c_int32 * L)(*[int(n) for n in n_ls_host]),
-         ptr(W0, _f32, "W0"), ptr(b0, _f32, "b0"), ptr(W1, _f32, "W1"), ptr(b1, _f32, "b1"), ptr(W2, _f32, "W2"), ptr(b2, _f32, "b2"),
-         ptr(out_rgb, _f32, "out_rgb"), ptr(out_image, _i32, "out_image"), int(rows), int(cols), int(origin[0]), int(origin[1]),
-         float(denom), L, F, C, int(bool(leaky)), stream_ptr())
+    C, pointers, scalars = _grid_model("render_grid", grid, n_ls, n_ls_host, decoder_params, leaky)
+    call("gngf_render_grid", *pointers, *_lattice_sink("render_grid", rows, cols, C, out_rgb, out_image), int(rows), int(cols),
+         int(origin[0]), int(origin[1]), float(denom), *scalars, stream_ptr())
 
 
 def check_query_xy(who, xy):
@@ -2345,49 +2353,23 @@ def query_points(tables, n_ls, decoder_params, xy, *, vert_idx=None, vert_w=None
     out_image (P, C) int32 is what render_lattice writes for a lattice point with the same float32 coordinate.  The model
     arguments are render_lattice's.  Everything is checked here, before any device work; no autograd, no workspace, no
     allocation, no synchronisation: capturable.  P = 0 launches nothing."""
-    L, T, F = tables.shape
-    W0, b0, W1, b1, W2, b2 = decoder_params
-    C = W2.shape[0]
-    if tuple(W0.shape) != (64, L * F) or tuple(W1.shape) != (64, 64) or W2.shape[1] != 64:
-        raise ValueError(f"query_points: decoder ({L * F} -> 64 -> 64 -> C) expected, got {tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
-    if n_ls.numel() != L:
-        raise ValueError(f"n_ls holds {n_ls.numel()} resolutions for {L} levels")
+    C, pointers, scalars = _table_model("query_points", tables, n_ls, decoder_params, vert_idx, vert_w, vstride, leaky, mode)
     P = _query_tail("query_points", xy, C, out_rgb, out_image)
-    vt = vert_idx is not None
-    K = check_topk(vert_idx.shape[1]) if vt else 0
-    tp, code = _tab(tables)
-    NV = int(vert_idx.shape[0]) if vt else 0
-    if vt and tuple(vert_w.shape) != (NV, K):
-        raise ValueError(f"vert_w must be (NV, K) = ({NV}, {K}), got {tuple(vert_w.shape)}")
     if P == 0:
         return
-    call("gngf_ext3_query", tp, code, ptr(vert_idx, _i32, "vert_idx"), ptr(vert_w, _f32, "vert_w"), ptr(n_ls, _i32, "n_ls"),
-         ptr(W0, _f32, "W0"), ptr(b0, _f32, "b0"), ptr(W1, _f32, "W1"), ptr(b1, _f32, "b1"), ptr(W2, _f32, "W2"), ptr(b2, _f32, "b2"),
-         L, F, T, K, index_source(vert_idx, mode), int(vstride), NV, C, int(bool(leaky)),
-         ptr(xy, _f32, "xy"), P, ptr(out_rgb, _f32, "out_rgb"), ptr(out_image, _i32, "out_image"), stream_ptr())
+    call("gngf_ext3_query", *pointers, *scalars, ptr(xy, _f32, "xy"), P, ptr(out_rgb, _f32, "out_rgb"),
+         ptr(out_image, _i32, "out_image"), stream_ptr())
 
 
 def query_grid_points(grid, n_ls, n_ls_host, decoder_params, xy, *, leaky=False, out_rgb=None, out_image=None):
     """query_points from a baked vertex grid (render_grid's model arguments; gngf_ext3_query_grid).  Corners are clamped to the
     level's grid, so no coordinate faults; only coordinates in [0, 1]^2 give the model's values."""
-    L = len(n_ls_host)
-    W0, b0, W1, b1, W2, b2 = decoder_params
-    C = W2.shape[0]
-    vtot = _grid_vertices(n_ls_host)
-    if grid.dim() != 2 or grid.shape[0] != vtot:
-        raise ValueError(f"query_grid_points: grid must be ({vtot}, F) for these resolutions, got {tuple(grid.shape)}")
-    F = int(grid.shape[1])
-    if tuple(W0.shape) != (64, L * F) or tuple(W1.shape) != (64, 64) or W2.shape[1] != 64:
-        raise ValueError(f"query_grid_points: decoder ({L * F} -> 64 -> 64 -> C) expected, got {tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
-    if n_ls.numel() != L:
-        raise ValueError(f"n_ls holds {n_ls.numel()} resolutions for {L} levels")
+    C, pointers, scalars = _grid_model("query_grid_points", grid, n_ls, n_ls_host, decoder_params, leaky)
     P = _query_tail("query_grid_points", xy, C, out_rgb, out_image)
     if P == 0:
         return
-    call("gngf_ext3_query_grid", ptr(grid, _f32, "grid"), ptr(n_ls, _i32, "n_ls"), (_ct.c_int32 * L)(*[int(n) for n in n_ls_host]),
-         ptr(W0, _f32, "W0"), ptr(b0, _f32, "b0"), ptr(W1, _f32, "W1"), ptr(b1, _f32, "b1"), ptr(W2, _f32, "W2"), ptr(b2, _f32, "b2"),
-         L, F, C, int(bool(leaky)), ptr(xy, _f32, "xy"), P, ptr(out_rgb, _f32, "out_rgb"), ptr(out_image, _i32, "out_image"),
-         stream_ptr())
+    call("gngf_ext3_query_grid", *pointers, *scalars, ptr(xy, _f32, "xy"), P, ptr(out_rgb, _f32, "out_rgb"),
+         ptr(out_image, _i32, "out_image"), stream_ptr())
 
 
 # Keep the decoder's activated hidden layers (512 B / pixel) from forward to backward instead of recomputing them: the

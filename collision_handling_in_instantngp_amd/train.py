@@ -2,6 +2,7 @@
 training loop: Loss (utils.py:78-174), get_optimizer (functions.py:96-127), train_step
 (functions.py:139-355, batching + loss assembly only; no wandb / plotting / collision diagnostics)."""
 import contextlib
+import math
 
 import numpy as np
 import torch
@@ -1409,27 +1410,45 @@ def _render_setup(net, rows, cols, denom, origin):
         denom = max(int(rows), int(cols)) - 1           # data.normalise_coordinates: the longer side spans [0, 1]
     rows, cols, r0, c0 = _check_lattice(rows, cols, denom, origin)
     C = _check_render_model(net, "render()")
-    if not net._hash_mode:
-        _check_unit_square(rows, cols, r0, c0, denom, "render(): GNGF indexing looks vertices up in the table")
-    elif getattr(net, "_dense_levels", False):
-        _check_unit_square(rows, cols, r0, c0, denom, "render(): a dense level clamps a vertex outside its grid, so the model is defined")
+    why = _unit_square_why(net, "render()")
+    if why is not None:
+        _check_unit_square(rows, cols, r0, c0, denom, why)
     return rows, cols, r0, c0, float(np.float32(denom)), C
 
 
-def _render_outputs(rows, cols, C, dev, rgb, image, out_rgb, out_image, who):
-    """The (out_rgb, out_image) a render writes — None where not asked for — new tensors on dev unless given; ValueError for a
-    buffer of the wrong kind or size."""
+def _forward_outputs(lead, C, dev, rgb, image, out_rgb, out_image, who):
+    """The (out_rgb, out_image) a forward-only call writes — None where not asked for — new tensors on dev unless given: rgb
+    (prod(lead), C) float32, image (*lead, C) int32 — (*lead) for one channel; lead = (rows, cols) of a render, (P,) of a query.
+    ValueError for a buffer of the wrong kind or size."""
     rgb, image = bool(rgb) or out_rgb is not None, bool(image) or out_image is not None
     if not (rgb or image):
         raise ValueError(f"{who}: ask for rgb, image or both")
+    n = math.prod(lead)
     for name, t, dt in (("out_rgb", out_rgb, torch.float32), ("out_image", out_image, torch.int32)):
-        if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() != rows * cols * C):
-            raise ValueError(f"{name} must be a contiguous device {dt} tensor of {rows} x {cols} x {C} elements")
+        if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() != n * C):
+            raise ValueError(f"{name} must be a contiguous device {dt} tensor of {' x '.join(str(s) for s in (*lead, C))} elements")
     if rgb and out_rgb is None:
-        out_rgb = torch.empty((rows * cols, C), dtype=torch.float32, device=dev)
+        out_rgb = torch.empty((n, C), dtype=torch.float32, device=dev)
     if image and out_image is None:
-        out_image = torch.empty((rows, cols, C) if C != 1 else (rows, cols), dtype=torch.int32, device=dev)
+        out_image = torch.empty((*lead, C) if C != 1 else tuple(lead), dtype=torch.int32, device=dev)
     return out_rgb, out_image
+
+
+def _asked_for(out_rgb, out_image):
+    """what a forward-only call returns: the pair, or whichever was asked for"""
+    if out_rgb is not None and out_image is not None:
+        return out_rgb, out_image
+    return out_rgb if out_rgb is not None else out_image
+
+
+def _unit_square_why(net, who):
+    """why `who` needs its coordinates inside [0, 1]^2 with this model's index source — None for plain hash indexing, which is
+    defined on the whole plane"""
+    if not net._hash_mode:
+        return f"{who}: GNGF indexing looks vertices up in the table"
+    if getattr(net, "_dense_levels", False):
+        return f"{who}: a dense level clamps a vertex outside its grid, so the model is defined"
+    return None
 
 
 @torch.no_grad()
@@ -1449,6 +1468,17 @@ def _render_vertex_table(net):
 
 
 @torch.no_grad()
+def _forward_model(net, tables):
+    """The model as the forward-only ops calls take it, once the caller has validated its own arguments (a trainable HPD is
+    evaluated here): ((tables, n_ls, decoder parameters), keywords) — tables = net.encoding.packed_tables(), the level
+    resolutions on their device, the six detached decoder tensors; vert_idx / vert_w / vstride (the vertex table of the current
+    HPD weights under GNGF indexing: _render_vertex_table), leaky and mode."""
+    ti, w, vstride = (None, None, 0) if net._hash_mode else _render_vertex_table(net)
+    return ((tables, net._n_ls_flat(tables.device), [p.detach() for p in net._decoder_params()]),
+            dict(vert_idx=ti, vert_w=w, vstride=vstride, leaky=net._leaky, mode=_index_source(net)))
+
+
+@torch.no_grad()
 def render(net, rows, cols, denom=None, origin=(0, 0), *, rgb=True, image=False, out_rgb=None, out_image=None):
     """The picture the model encodes NOW, on the lattice ((origin[0] + r) / denom, (origin[1] + c) / denom), r < rows,
     c < cols: one launch of gngf_render — no coordinate tensor, no binning, no (P, L F) encoding in memory, none of the
@@ -1464,33 +1494,10 @@ def render(net, rows, cols, denom=None, origin=(0, 0), *, rgb=True, image=False,
     net(x) is the general path."""
     rows, cols, r0, c0, denom, C = _render_setup(net, rows, cols, denom, origin)
     tables = net.encoding.packed_tables()
-    dev = tables.device
-    out_rgb, out_image = _render_outputs(rows, cols, C, dev, rgb, image, out_rgb, out_image, "render()")
-    ti = w = None
-    vstride = 0
-    if not net._hash_mode:
-        ti, w, vstride = _render_vertex_table(net)
-    ops.render_lattice(tables, net._n_ls_flat(dev), [p.detach() for p in net._decoder_params()], rows, cols, denom, (r0, c0),
-                       vert_idx=ti, vert_w=w, vstride=vstride, leaky=net._leaky, out_rgb=out_rgb, out_image=out_image,
-                       mode=_index_source(net))
-    if out_rgb is not None and out_image is not None:
-        return out_rgb, out_image
-    return out_rgb if out_rgb is not None else out_image
-
-
-def _query_outputs(P, C, dev, rgb, image, out_rgb, out_image, who):
-    """_render_outputs for P points: rgb (P, C) float32, image (P, C) int32 — (P,) for one channel"""
-    rgb, image = bool(rgb) or out_rgb is not None, bool(image) or out_image is not None
-    if not (rgb or image):
-        raise ValueError(f"{who}: ask for rgb, image or both")
-    for name, t, dt in (("out_rgb", out_rgb, torch.float32), ("out_image", out_image, torch.int32)):
-        if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() != P * C):
-            raise ValueError(f"{name} must be a contiguous device {dt} tensor of {P} x {C} elements")
-    if rgb and out_rgb is None:
-        out_rgb = torch.empty((P, C), dtype=torch.float32, device=dev)
-    if image and out_image is None:
-        out_image = torch.empty((P, C) if C != 1 else (P,), dtype=torch.int32, device=dev)
-    return out_rgb, out_image
+    out_rgb, out_image = _forward_outputs((rows, cols), C, tables.device, rgb, image, out_rgb, out_image, "render()")
+    model, kw = _forward_model(net, tables)
+    ops.render_lattice(*model, rows, cols, denom, (r0, c0), out_rgb=out_rgb, out_image=out_image, **kw)
+    return _asked_for(out_rgb, out_image)
 
 
 def _check_query_coordinates(xy, who, unit_square_why):
@@ -1522,27 +1529,15 @@ def query(net, xy, *, rgb=True, image=False, out_rgb=None, out_image=None, check
     L * F > 64, F not in {1, 2, 4}: net(x) is the general path — and for an xy of another kind."""
     C = _check_render_model(net, "query()")
     P = ops.check_query_xy("query()", xy)
-    out_rgb, out_image = _query_outputs(P, C, xy.device, rgb, image, out_rgb, out_image, "query()")
+    out_rgb, out_image = _forward_outputs((P,), C, xy.device, rgb, image, out_rgb, out_image, "query()")
     if check:
-        why = None
-        if not net._hash_mode:
-            why = "query(): GNGF indexing looks vertices up in the table"
-        elif getattr(net, "_dense_levels", False):
-            why = "query(): a dense level clamps a vertex outside its grid, so the model is defined"
-        _check_query_coordinates(xy, "query()", why)
+        _check_query_coordinates(xy, "query()", _unit_square_why(net, "query()"))
     tables = net.encoding.packed_tables()
     if tables.device != xy.device:
         raise ValueError(f"query(): xy is on {xy.device}, the model on {tables.device}")
-    ti = w = None
-    vstride = 0
-    if not net._hash_mode:
-        ti, w, vstride = _render_vertex_table(net)
-    ops.query_points(tables, net._n_ls_flat(tables.device), [p.detach() for p in net._decoder_params()], xy,
-                     vert_idx=ti, vert_w=w, vstride=vstride, leaky=net._leaky, out_rgb=out_rgb, out_image=out_image,
-                     mode=_index_source(net))
-    if out_rgb is not None and out_image is not None:
-        return out_rgb, out_image
-    return out_rgb if out_rgb is not None else out_image
+    model, kw = _forward_model(net, tables)
+    ops.query_points(*model, xy, out_rgb=out_rgb, out_image=out_image, **kw)
+    return _asked_for(out_rgb, out_image)
 
 
 def _score_render(render_image, out_dim, og_image):
@@ -1632,10 +1627,9 @@ def _score_setup(net, image, step, denom, who):
     C = _check_render_model(net, who)
     if Ci != C:
         raise ValueError(f"{who}: the image has {Ci} channel(s), the model {C}" + _GENERAL_PATH)
-    if not net._hash_mode:
-        _check_unit_square(h, w, 0, 0, denom, f"{who}: GNGF indexing looks vertices up in the table")
-    elif getattr(net, "_dense_levels", False):
-        _check_unit_square(h, w, 0, 0, denom, f"{who}: a dense level clamps a vertex outside its grid, so the model is defined")
+    why = _unit_square_why(net, who)
+    if why is not None:
+        _check_unit_square(h, w, 0, 0, denom, why)
     return img, float(np.float32(denom)), step
 
 
@@ -1664,12 +1658,8 @@ def score(net, image, *, step=1, denom=None, out=None):
     ws = getattr(net, "_score_workspace", None)
     if ws is None or ws.device != dev:
         ws = net._score_workspace = ops.render_score_workspace(dev)
-    ti = w = None
-    vstride = 0
-    if not net._hash_mode:
-        ti, w, vstride = _render_vertex_table(net)
-    ops.render_score(tables, net._n_ls_flat(dev), [p.detach() for p in net._decoder_params()], img, denom=denom, step=step,
-                     sums=out, workspace=ws, vert_idx=ti, vert_w=w, vstride=vstride, leaky=net._leaky, mode=_index_source(net))
+    model, kw = _forward_model(net, tables)
+    ops.render_score(*model, img, denom=denom, step=step, sums=out, workspace=ws, **kw)
     return out
 
 
@@ -1787,15 +1777,7 @@ def fit_sampled(net, loss_fn, optimizer, sampler, *, rounds, steps_per_round, to
 # Baking: once training stops, sum_k w[v, k] table[l, idx[v, k]] is a constant of the (level, vertex) — the vertex grid of a
 # training step, over all L levels.  A BakedGrid holds that grid and a copy of the decoder: the picture without the model.
 
-def baked_level_offsets(n_ls_host):
-    """(offsets, vtot) of a baked grid: level l's (N_l + 2) x (N_l + 2) vertices are rows offsets[l] + gy (N_l + 2) + gx of the
-    (vtot, F) grid, offsets[l] = sum_{j<l} (N_j + 2)^2 (include/gngf.h: gngf_vertex_grid_fwd).  A coordinate in [0, 1] reaches
-    corners 0 .. floor(N_l) + 1 = N_l + 1 per axis: all inside the level."""
-    offsets, vtot = [], 0
-    for n in n_ls_host:
-        offsets.append(vtot)
-        vtot += (int(n) + 2) ** 2
-    return offsets, vtot
+baked_level_offsets = ops.baked_level_offsets       # (offsets, vtot) of a baked grid: the one statement of its layout in Python
 
 
 class BakedGrid:
@@ -1836,13 +1818,11 @@ class BakedGrid:
             denom = max(int(rows), int(cols)) - 1
         rows, cols, r0, c0 = _check_lattice(rows, cols, denom, origin)
         _check_unit_square(rows, cols, r0, c0, denom, "BakedGrid.render(): a baked model holds the vertices of its levels")
-        out_rgb, out_image = _render_outputs(rows, cols, self.out_dim, self.grid.device, rgb, image, out_rgb, out_image,
-                                             "BakedGrid.render()")
+        out_rgb, out_image = _forward_outputs((rows, cols), self.out_dim, self.grid.device, rgb, image, out_rgb, out_image,
+                                              "BakedGrid.render()")
         ops.render_grid(self.grid, self.n_ls, self.n_ls_host, self.decoder, rows, cols, float(np.float32(denom)), (r0, c0),
                         leaky=self.leaky, out_rgb=out_rgb, out_image=out_image)
-        if out_rgb is not None and out_image is not None:
-            return out_rgb, out_image
-        return out_rgb if out_rgb is not None else out_image
+        return _asked_for(out_rgb, out_image)
 
     @torch.no_grad()
     def query(self, xy, *, rgb=True, image=False, out_rgb=None, out_image=None, check=True):
@@ -1853,14 +1833,12 @@ class BakedGrid:
         P = ops.check_query_xy("BakedGrid.query()", xy)
         if xy.device != self.grid.device:
             raise ValueError(f"BakedGrid.query(): xy is on {xy.device}, the grid on {self.grid.device}")
-        out_rgb, out_image = _query_outputs(P, self.out_dim, xy.device, rgb, image, out_rgb, out_image, "BakedGrid.query()")
+        out_rgb, out_image = _forward_outputs((P,), self.out_dim, xy.device, rgb, image, out_rgb, out_image, "BakedGrid.query()")
         if check:
             _check_query_coordinates(xy, "BakedGrid.query()", "BakedGrid.query(): a baked model holds the vertices of its levels")
         ops.query_grid_points(self.grid, self.n_ls, self.n_ls_host, self.decoder, xy, leaky=self.leaky, out_rgb=out_rgb,
                               out_image=out_image)
-        if out_rgb is not None and out_image is not None:
-            return out_rgb, out_image
-        return out_rgb if out_rgb is not None else out_image
+        return _asked_for(out_rgb, out_image)
 
     def render_psnr(self, og_image):
         """train.render_psnr of the baked picture: (image, psnr, accuracy)."""
@@ -1882,20 +1860,18 @@ def bake(net, *, out=None):
     tables = net.encoding.packed_tables()
     dev = tables.device
     L, T, F = tables.shape
-    dec = [p.detach() for p in net._decoder_params()]
     n_ls_host = list(net._n_ls_host)
     if out is None:
         out = BakedGrid(torch.empty((baked_level_offsets(n_ls_host)[1], F), dtype=torch.float32, device=dev),
-                        [torch.empty(p.shape, dtype=torch.float32, device=dev) for p in dec], n_ls_host, net._leaky)
+                        [torch.empty(p.shape, dtype=torch.float32, device=dev) for p in net._decoder_params()], n_ls_host,
+                        net._leaky)
     elif not isinstance(out, BakedGrid) or out.n_ls_host != n_ls_host or (out.F, out.out_dim, out.leaky) != (F, C, net._leaky) \
             or out.grid.device != dev:
         raise ValueError("bake(): out must be a BakedGrid of this model's shape (resolutions, F, outputs, activation) on its device")
-    ti = w = None
-    vstride = NV = K = 0
-    if not net._hash_mode:
-        ti, w, vstride = _render_vertex_table(net)
-        NV, K = int(ti.shape[0]), int(ti.shape[1])
-    ops.bake_vertex_grid(tables, out.n_ls, n_ls_host, ti, w, vstride, NV, F, T, K, out=out.grid, mode=_index_source(net))
+    (_, _, dec), kw = _forward_model(net, tables)
+    ti = kw["vert_idx"]
+    NV, K = (0, 0) if ti is None else (int(ti.shape[0]), int(ti.shape[1]))
+    ops.bake_vertex_grid(tables, out.n_ls, n_ls_host, ti, kw["vert_w"], kw["vstride"], NV, F, T, K, out=out.grid, mode=kw["mode"])
     for d, s in zip(out.decoder, dec):
         d.copy_(s)
     return out

@@ -181,12 +181,8 @@ def raw_model(name):
     """the arguments of ops.render_score for a model: (tables, n_ls, decoder parameters, keywords)"""
     from collision_handling_in_instantngp_amd import train
     net, c = build(name)
-    tables = net.encoding.packed_tables()
-    kw = dict(leaky=net._leaky, mode=train._index_source(net))
-    if not net._hash_mode:
-        ti, vw, vstride = train._render_vertex_table(net)
-        kw.update(vert_idx=ti, vert_w=vw, vstride=vstride)
-    return net, tables, net._n_ls_flat(tables.device), [p.detach() for p in net._decoder_params()], kw
+    (tables, n_ls, dec), kw = train._forward_model(net, net.encoding.packed_tables())
+    return net, tables, n_ls, dec, kw
 
 
 @pytest.mark.parametrize("name", ["hash-L16F2", "gngf-frozen-K4", "hash-L16F4"])
