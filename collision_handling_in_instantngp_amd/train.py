@@ -431,6 +431,37 @@ def assemble_loss(mse, kls, colls, l_mse, l_js_kl, l_collisions):
     return loss
 
 
+def _capture_guarded(body):
+    """(graph, body()) with body's launches captured into a torch.cuda.CUDAGraph: the one capture of this module, for a training
+    step (GraphedStep._capture) and for a body that is none (a captured score()).  Warm body up eagerly first: what it allocates
+    must exist before the capture."""
+    import gc
+    g = torch.cuda.CUDAGraph()
+    # No garbage collection while the stream captures: a collection that happens to run inside the body finalises whatever
+    # cyclic garbage earlier work left behind (other models' graphs, events, blocks last used on other streams), and a
+    # finaliser that touches the runtime during a capture aborts the process (seen once in round 5: "Fatal Python error:
+    # Aborted ... Garbage-collecting" in the middle of a captured forward pass).  torch.cuda.graph collects once on entry;
+    # what the body itself leaves behind is collected after the capture has ended.
+    gc_was_on = gc.isenabled()
+    gc.disable()
+    try:
+        # thread_local: other threads of the process (the RCCL watchdog at world > 1) may query events while we capture
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            result = body()
+    finally:
+        if gc_was_on:
+            gc.enable()
+    return g, result
+
+
+def _previous(previous_collisions, previous_min_possible_collisions, dev):
+    """(previous_collisions, previous_min_possible_collisions) on dev, None as the empty tensor the first epoch hands the loss
+    (assemble_loss: functions.py:243-245)"""
+    empty = torch.tensor([], device=dev)
+    return (empty if previous_collisions is None else previous_collisions.to(dev),
+            empty if previous_min_possible_collisions is None else previous_min_possible_collisions.to(dev))
+
+
 class GraphedStep:
     """One optimisation step — zero_grad, net(batch), Loss, the weighted sum of functions.py:243-245, backward and
     optimizer.step() — captured ONCE into a hipGraph per batch shape and replayed for every further batch: the step is
@@ -582,32 +613,22 @@ class GraphedStep:
             self.optimizer.prepare_capture(self.unroll)
         if pipe is not None:
             pipe.reset()
-        g = torch.cuda.CUDAGraph()
-        results = []
-        # No garbage collection while the stream captures: a collection that happens to run inside the body finalises whatever
-        # cyclic garbage earlier work left behind (other models' graphs, events, blocks last used on other streams), and a
-        # finaliser that touches the runtime during a capture aborts the process (seen once in round 5: "Fatal Python error:
-        # Aborted ... Garbage-collecting" in the middle of a captured forward pass).  torch.cuda.graph() collects once on entry;
-        # what the body itself leaves behind is collected after the capture has ended.
-        import gc
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
-            # thread_local: other threads of the process (the RCCL watchdog at world > 1) may query events while we capture
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                subs = [st] + st["more"]
-                for j, sub in enumerate(subs):
-                    last = j + 1 == len(subs)
-                    # step j's pixel-stage launches bin step j + 1's batch (its own static buffer: refilled before every replay);
-                    # the last step's bin the first batch of the NEXT replay (cross_replay: the caller puts it into x_next beforehand)
-                    nx = subs[j + 1]["x"] if not last else (st["x_next"] if W is not None else None)
-                    results.append(self._body(sub, next_x=nx, next_ws=(W[fills] if (last and W is not None) else None),
-                                              binned_in=(W[reads] if (j == 0 and W is not None and reads is not None) else None)))
-                    if self.optimizer is not None:
-                        self.optimizer.step()
-        finally:
-            if gc_was_on:
-                gc.enable()
+
+        def steps():
+            results = []
+            subs = [st] + st["more"]
+            for j, sub in enumerate(subs):
+                last = j + 1 == len(subs)
+                # step j's pixel-stage launches bin step j + 1's batch (its own static buffer: refilled before every replay);
+                # the last step's bin the first batch of the NEXT replay (cross_replay: the caller puts it into x_next beforehand)
+                nx = subs[j + 1]["x"] if not last else (st["x_next"] if W is not None else None)
+                results.append(self._body(sub, next_x=nx, next_ws=(W[fills] if (last and W is not None) else None),
+                                          binned_in=(W[reads] if (j == 0 and W is not None and reads is not None) else None)))
+                if self.optimizer is not None:
+                    self.optimizer.step()
+            return results
+
+        g, results = _capture_guarded(steps)
         if pipe is not None:
             pipe.reset()
         st["variants"][name] = (g, results, self._handover(st))
@@ -679,10 +700,7 @@ class GraphedStep:
         if len(batches) != self.unroll:
             raise ValueError(f"run_many needs exactly unroll = {self.unroll} batches")
         (x0, y0) = batches[0]
-        dev = x0.device
-        empty = torch.tensor([], device=dev)
-        pc = empty if previous_collisions is None else previous_collisions.to(dev)
-        pm = empty if previous_min_possible_collisions is None else previous_min_possible_collisions.to(dev)
+        pc, pm = _previous(previous_collisions, previous_min_possible_collisions, x0.device)
         key = (tuple(x0.shape), tuple(y0.shape), tuple(pc.shape), tuple(pm.shape), bool(models.should_use_hash_function))
         st = self._graphs.get(key)
         if st is None:
@@ -710,17 +728,37 @@ class GraphedStep:
         return results[0]
 
     def __call__(self, batch_x, batch_target, previous_collisions=None, previous_min_possible_collisions=None, next_first=None):
-        dev = batch_x.device
-        empty = torch.tensor([], device=dev)
-        pc = empty if previous_collisions is None else previous_collisions.to(dev)
-        pm = empty if previous_min_possible_collisions is None else previous_min_possible_collisions.to(dev)
-        key = (tuple(batch_x.shape), tuple(batch_target.shape), tuple(pc.shape), tuple(pm.shape), bool(models.should_use_hash_function))
         if self.unroll != 1:
             raise ValueError("an unrolled GraphedStep takes its batches through run_many()")
-        st = self._graphs.get(key)
-        if st is None:
-            st = self._build(key, batch_x, batch_target, pc, pm)
-        return self._replay(st, [(batch_x, batch_target)], pc, pm, next_first)[0]
+        return self.run_many([(batch_x, batch_target)], previous_collisions, previous_min_possible_collisions, next_first)[0]
+
+
+def _graphed_step_for(net, loss_fn, optimizer, weights, batch_percentage, rest, coord_bounds):
+    """The GraphedStep (cross_replay) of this net and configuration, cached on net._graphed_step: built anew when the loss, the
+    optimizer, the weights (l_mse, l_js_kl, l_collisions), batch_percentage or `rest` — what else the caller's steps depend on
+    — differ from the cached one's.  coord_bounds: called only when a step is built (train_epoch's reads the device)."""
+    gs = getattr(net, "_graphed_step", None)
+    cfg = (id(loss_fn), id(optimizer), *weights, batch_percentage, *rest)
+    if gs is None or gs._cfg != cfg:
+        gs = GraphedStep(net, loss_fn, optimizer, *weights, batch_percentage, coord_bounds=coord_bounds(), cross_replay=True)
+        gs._cfg = cfg
+        net._graphed_step = gs
+    return gs
+
+
+def _eager_step(net, loss_fn, optimizer, bx, by, pc, pm, weights, one, batch_percentage=1.0, should_calc_counts=False):
+    """One optimisation step launch by launch: zero_grad -> net -> Loss -> weighted sum -> backward -> step (functions.py:199-250).
+    one: the seed of backward(), d loss / d loss = 1 as a device scalar — no fill per batch.
+    Returns (out, idx, loss, mse, kls, colls, counts)."""
+    optimizer.zero_grad()
+    by = by.contiguous()
+    with (net.fused_mse(by, gloss=promised_gloss(loss_fn, weights[0])) if hasattr(net, "fused_mse") else contextlib.nullcontext()):
+        out, probs, idx, counts = net(bx, batch_percentage, should_calc_counts=should_calc_counts)
+    mse, kls, colls = loss_fn(out, by, None if probs is None else probs.shape[-1], probs, pc, pm)
+    loss = assemble_loss(mse, kls, colls, *weights)
+    loss.backward(gradient=one.to(loss.dtype))
+    optimizer.step()
+    return out, idx, loss, mse, kls, colls, counts
 
 
 def train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_collisions, batch_percentage=1.0,
@@ -742,9 +780,8 @@ def train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_coll
     num_batches = int(np.ceil(shape / (shape * batch_percentage)))
     step = int(batch_percentage * shape)
     dev = x.device
-    empty = torch.tensor([], device=dev)
-    previous_collisions = empty if previous_collisions is None else previous_collisions.to(dev)
-    previous_min_possible_collisions = empty if previous_min_possible_collisions is None else previous_min_possible_collisions.to(dev)
+    pc, pm = _previous(previous_collisions, previous_min_possible_collisions, dev)
+    weights = (l_mse, l_js_kl, l_collisions)
     outputs = torch.zeros((shape, target.shape[1]), device=dev)     # (the reference leaves unvisited rows uninitialised)
     indices = None
     rec = {"loss": [], "mse": [], "kls": [], "colls": [], "counts": []}
@@ -761,14 +798,9 @@ def train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_coll
     rec["tracked"] = tracked
     gs = None
     if graph:
-        gs = getattr(net, "_graphed_step", None)
-        cfg = (id(loss_fn), id(optimizer), l_mse, l_js_kl, l_collisions, batch_percentage, tracked)
-        if gs is None or gs._cfg != cfg:
-            bounds = None if models.should_use_hash_function else (float(x[:, 0].max()), float(x[:, 1].max()))
-            gs = GraphedStep(net, loss_fn, optimizer, l_mse, l_js_kl, l_collisions, batch_percentage, coord_bounds=bounds,
-                             cross_replay=True)
-            gs._cfg = cfg
-            net._graphed_step = gs
+        gs = _graphed_step_for(net, loss_fn, optimizer, weights, batch_percentage, (tracked,), lambda: (
+            None if models.should_use_hash_function else (float(x[:, 0].max()), float(x[:, 1].max()))))
+
     def batch(b):
         lo_, hi_ = b * step, (b + 1) * step
         sel = shuffled_indices[lo_:hi_].long() if should_shuffle else slice(lo_, hi_)
@@ -790,18 +822,11 @@ def train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_coll
         if gs is not None and not should_calc_counts:
             # (the next slice is named a step ahead: this replay's launches bin it, the next replay starts on binned pixels)
             nf = upcoming[0] if (upcoming is not None and upcoming[0].shape == bx.shape) else None
-            r = gs(bx, by, previous_collisions, previous_min_possible_collisions, next_first=nf)
+            r = gs(bx, by, pc, pm, next_first=nf)
             out, idx, loss, mse, kls, colls, counts = r.out, r.idx, r.loss, r.mse, r.kls, r.colls, []
         else:
-            optimizer.zero_grad()
-            by = by.contiguous()
-            with (net.fused_mse(by, gloss=promised_gloss(loss_fn, l_mse)) if hasattr(net, "fused_mse") else contextlib.nullcontext()):
-                out, probs, idx, counts = net(bx, batch_percentage, should_calc_counts=should_calc_counts)
-            mse, kls, colls = loss_fn(out, by, None if probs is None else probs.shape[-1], probs,
-                                      previous_collisions, previous_min_possible_collisions)
-            loss = assemble_loss(mse, kls, colls, l_mse, l_js_kl, l_collisions)
-            loss.backward(gradient=one.to(loss.dtype))
-            optimizer.step()
+            out, idx, loss, mse, kls, colls, counts = _eager_step(net, loss_fn, optimizer, bx, by, pc, pm, weights, one,
+                                                                  batch_percentage, should_calc_counts)
         outputs[lo:lo + out.shape[0]] = out.detach()
         if image is not None:
             image.add(out.detach(), lo)
@@ -847,9 +872,8 @@ def train_sampled(net, loss_fn, optimizer, sampler, steps, *, l_mse, l_js_kl, l_
         raise ValueError("train_sampled draws batch k + 1 while batch k is in use: the sampler needs buffers >= 2")
     net.train()
     dev = sampler.image.device
-    empty = torch.tensor([], device=dev)
-    previous_collisions = empty if previous_collisions is None else previous_collisions.to(dev)
-    previous_min_possible_collisions = empty if previous_min_possible_collisions is None else previous_min_possible_collisions.to(dev)
+    pc, pm = _previous(previous_collisions, previous_min_possible_collisions, dev)
+    weights = (l_mse, l_js_kl, l_collisions)
     losses = torch.zeros((steps,), device=dev)
     mses = torch.zeros((steps,), device=dev)
     if steps == 0:
@@ -858,13 +882,8 @@ def train_sampled(net, loss_fn, optimizer, sampler, steps, *, l_mse, l_js_kl, l_
         net.stop_collision_tracking()
     gs = None
     if graph:
-        gs = getattr(net, "_graphed_step", None)
-        cfg = (id(loss_fn), id(optimizer), l_mse, l_js_kl, l_collisions, 1.0, False, "sampled", tuple(sampler.coord_bounds))
-        if gs is None or gs._cfg != cfg:
-            gs = GraphedStep(net, loss_fn, optimizer, l_mse, l_js_kl, l_collisions, 1.0, coord_bounds=sampler.coord_bounds,
-                             cross_replay=True)
-            gs._cfg = cfg
-            net._graphed_step = gs
+        gs = _graphed_step_for(net, loss_fn, optimizer, weights, 1.0, (False, "sampled", tuple(sampler.coord_bounds)),
+                               lambda: sampler.coord_bounds)
     one = torch.ones((), device=dev)
     pipe = getattr(dp, "pipeline", None)
     upcoming = sampler.next()
@@ -872,19 +891,12 @@ def train_sampled(net, loss_fn, optimizer, sampler, steps, *, l_mse, l_js_kl, l_
         bx, by = upcoming
         upcoming = sampler.next()                    # batch k + 1, in the other buffer pair: batch k stays as it is
         if gs is not None:
-            r = gs(bx, by, previous_collisions, previous_min_possible_collisions, next_first=upcoming[0])
+            r = gs(bx, by, pc, pm, next_first=upcoming[0])
             loss, mse = r.loss, r.mse
         else:
             if pipe is not None:
                 pipe.announce(upcoming[0] if k + 1 < steps else None)
-            optimizer.zero_grad()
-            with (net.fused_mse(by, gloss=promised_gloss(loss_fn, l_mse)) if hasattr(net, "fused_mse") else contextlib.nullcontext()):
-                out, probs, _idx, _counts = net(bx, 1.0, should_calc_counts=False)
-            mse, kls, colls = loss_fn(out, by, None if probs is None else probs.shape[-1], probs,
-                                      previous_collisions, previous_min_possible_collisions)
-            loss = assemble_loss(mse, kls, colls, l_mse, l_js_kl, l_collisions)
-            loss.backward(gradient=one.to(loss.dtype))
-            optimizer.step()
+            _out, _idx, loss, mse, _kls, _colls, _counts = _eager_step(net, loss_fn, optimizer, bx, by, pc, pm, weights, one)
         losses[k].copy_(loss.detach())
         mses[k].copy_(mse.detach())
     return {"loss": losses, "mse": mses}
@@ -1107,6 +1119,11 @@ def new_epoch_state(best_sse0):
     return st
 
 
+def epoch_state_tensor(best_sse0, device):
+    """new_epoch_state's record as gngf_epoch_tail takes it: 128 bytes on the device"""
+    return torch.from_numpy(new_epoch_state(best_sse0).reshape(1).view(np.uint8).copy()).to(device)
+
+
 def levels_free_of_collisions(used, nverts, hash_source):
     """The check of functions.py:684 on the distinct-slot counts used (Kc, L): are the last two levels (the one level when
     L = 1) free of collisions?  Hash source: nverts - used == 0; GNGF: mean over k clamped at 0 equals 0, i.e. the integer
@@ -1250,6 +1267,69 @@ def _refuse_host_state(optimizer):
                          "part — use train.FusedAdam (get_optimizer's choice on the GPU)")
 
 
+class _EpochLoop:
+    """The device side of an epoch loop, shared by fit() and fit_sampled() (whose "epochs" are rounds): the state record of
+    gngf_epoch_tail and its take / last / finished words, the pinned word a poll reads, the two logs, the `best` and `final`
+    snapshots, and the count of rounds issued.  Per round the caller runs its steps and then calls tail(), then stop(); after its
+    loop, result().  n_elems, peak_term: what the PSNR is formed with; limit: the number of rounds at most; hash_source, tolerance,
+    min_delta, should_reset: gngf_epoch_tail's."""
+
+    def __init__(self, net, optimizer, dev, *, limit, n_elems, peak_term, poll_every, exact_final, **tail):
+        self.net, self.optimizer, self.dev, self.limit, self.tail_kw = net, optimizer, dev, limit, tail
+        self.n_elems, self.peak_term, self.poll_every, self.exact_final = n_elems, peak_term, poll_every, exact_final
+        self.L = net._num_levels
+        self.nverts = torch.from_numpy(np.asarray(net._level_vertex_counts(), dtype=np.int64)).to(dev)
+        self.state = epoch_state_tensor(sse_limit0(n_elems, peak_term), dev)
+        flags = self.state.view(torch.int32)
+        self.take, self.last, self.finished = flags[0:1], flags[1:2], flags[2:3]
+        self.polled = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
+        self.logf = self.logi = self.best = self.final = None
+        self.Kc = self.issued = 0
+
+    def tail(self, loss, mse, kls, colls, sums, used):
+        """after a round's steps: one launch of gngf_epoch_tail on the round's per-step loss / mse (kls, colls: None or per step),
+        the image's sums and the distinct-slot counts used (Kc, L) | None, then the predicated copies into the snapshots"""
+        if self.best is None:
+            # the optimizer's state exists now (the first step has run): the shadows are allocated once, here
+            tensors = state_tensors(self.net, self.optimizer)
+            self.best = DeviceSnapshot(tensors)
+            self.final = DeviceSnapshot(tensors) if self.exact_final else None
+            self.Kc = 0 if used is None else int(used.shape[0])
+            self.logf = torch.full((self.limit, 2 + 2 * self.L), float("nan"), dtype=torch.float64, device=self.dev)
+            self.logi = torch.zeros((self.limit, 6 + self.Kc * self.L), dtype=torch.int64, device=self.dev)
+        ops.epoch_tail(self.state, self.logf, self.logi, loss, mse, kls, colls, sums, used, self.nverts, epochs=self.limit, **self.tail_kw)
+        self.best.take_if(self.take)
+        if self.final is not None:
+            self.final.take_if(self.last)
+        self.issued += 1
+
+    def stop(self):
+        """every poll_every rounds, and after the last: one word read back — the loop's only synchronisation.  True: the device
+        has finished, issue no more."""
+        if self.issued % self.poll_every != 0 and self.issued != self.limit:
+            return False
+        self.polled.copy_(self.finished, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return int(self.polled[0]) != 0
+
+    def result(self):
+        """the FitResult; rounds issued past the device's last one are undone from the `final` snapshot"""
+        st = self.state.cpu().numpy().view(EPOCH_STATE)[0]
+        last_epoch, best_epoch = int(st["last_epoch"]), int(st["best_epoch"])
+        restored = False
+        if self.issued > last_epoch + 1 and self.final is not None:
+            self.final.restore()
+            restored = True
+        n, L = last_epoch + 1, self.L
+        lf, li = self.logf[:n].cpu().numpy(), self.logi[:n].cpu().numpy()
+        log = {"loss": lf[:, 0], "mse": lf[:, 1], "kls": lf[:, 2:2 + L], "colls_loss": lf[:, 2 + L:2 + 2 * L], "eq": li[:, 0],
+               "sse": li[:, 1], "counter": li[:, 2], "saved": li[:, 3].astype(bool), "stopper_fired": li[:, 4].astype(bool),
+               "zero_stop": li[:, 5].astype(bool), "used": li[:, 6:].reshape(n, self.Kc, L)}
+        log["psnr"] = np.array([float(psnr_from_sums(s, self.n_elems, self.peak_term)) for s in log["sse"]], dtype=np.float64)
+        log["accuracy"] = np.array([float((q / self.n_elems) * 100) for q in log["eq"]], dtype=np.float64)
+        return FitResult(log, last_epoch, best_epoch, STOP_REASONS[int(st["reason"])], self.best, self.issued, restored)
+
+
 def fit(net, loss_fn, optimizer, x, target, w, h, og_image, *, epochs, tolerance, min_delta, should_reset=True, l_mse, l_js_kl,
         l_collisions, batch_percentage=1.0, should_shuffle=True, shuffled_indices=None, graph=True, poll_every=16,
         exact_final=True, after_epoch=None):
@@ -1278,18 +1358,12 @@ def fit(net, loss_fn, optimizer, x, target, w, h, og_image, *, epochs, tolerance
                          f"PSNR comparison for n * 255^2 <= 2^44 only (DESIGN.md §3)")
     hash_mode = bool(models.should_use_hash_function)
     L = net._num_levels
+    loop = _EpochLoop(net, optimizer, dev, limit=epochs, n_elems=image.n_elems, peak_term=image.peak_term, poll_every=poll_every,
+                      exact_final=exact_final, hash_source=hash_mode, tolerance=tolerance, min_delta=min_delta, should_reset=should_reset)
+    nverts_f = loop.nverts.to(torch.float32)
     nverts_host = np.asarray(net._level_vertex_counts(), dtype=np.int64)
-    nverts = torch.from_numpy(nverts_host).to(dev)
-    nverts_f = nverts.to(torch.float32)
     min_possible = torch.from_numpy(np.maximum(nverts_host - net._hash_table_size, 0)).to(dev)
-    state = torch.from_numpy(new_epoch_state(sse_limit0(image.n_elems, image.peak_term)).reshape(1).view(np.uint8).copy()).to(dev)
-    flags = state.view(torch.int32)
-    take, last, finished = flags[0:1], flags[1:2], flags[2:3]
-    polled = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
-    logf = logi = best = final = None
-    Kc = 0
     pc = pm = None
-    issued = 0
     for e in range(epochs):
         rec = train_epoch(net, loss_fn, optimizer, x, target, w, h, l_mse, l_js_kl, l_collisions, batch_percentage=batch_percentage,
                           should_shuffle=should_shuffle, shuffled_indices=shuffled_indices, previous_collisions=pc,
@@ -1297,48 +1371,19 @@ def fit(net, loss_fn, optimizer, x, target, w, h, og_image, *, epochs, tolerance
         used = rec.get("used")
         if used is None and rec["indices"] is not None:
             used = net._distinct_slot_counts(rec["indices"], L, net._hash_table_size)
-        if best is None:
-            # the optimizer's state exists now (the first step has run): the shadows are allocated once, here
-            tensors = state_tensors(net, optimizer)
-            best = DeviceSnapshot(tensors)
-            final = DeviceSnapshot(tensors) if exact_final else None
-            Kc = 0 if used is None else int(used.shape[0])
-            logf = torch.full((epochs, 2 + 2 * L), float("nan"), dtype=torch.float64, device=dev)
-            logi = torch.zeros((epochs, 6 + Kc * L), dtype=torch.int64, device=dev)
         no_dist = hash_mode or not rec["kls"]
-        ops.epoch_tail(state, logf, logi, torch.stack(rec["loss"]).float(), torch.stack(rec["mse"]).float(),
-                       None if no_dist else torch.stack(rec["kls"]).float(), None if no_dist else torch.stack(rec["colls"]).float(),
-                       image.sums(), used, nverts, hash_source=hash_mode, tolerance=tolerance, min_delta=min_delta,
-                       should_reset=should_reset, epochs=epochs)
-        best.take_if(take)
-        if final is not None:
-            final.take_if(last)
+        loop.tail(torch.stack(rec["loss"]).float(), torch.stack(rec["mse"]).float(),
+                  None if no_dist else torch.stack(rec["kls"]).float(), None if no_dist else torch.stack(rec["colls"]).float(),
+                  image.sums(), used)
         if used is not None and not hash_mode:
             # the next epoch's previous_collisions (functions.py:678-679; models.py:597-607), formed on the device
             pc = (nverts_f[None, :] - used.to(torch.float32)).mean(0).clamp_min_(0)
             pm = min_possible
-        issued = e + 1
         if after_epoch is not None:
             after_epoch(e)
-        if issued % poll_every == 0 or issued == epochs:
-            polled.copy_(finished, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            if int(polled[0]) != 0:
-                break
-    st = state.cpu().numpy().view(EPOCH_STATE)[0]
-    last_epoch, best_epoch = int(st["last_epoch"]), int(st["best_epoch"])
-    restored = False
-    if issued > last_epoch + 1 and final is not None:
-        final.restore()
-        restored = True
-    n = last_epoch + 1
-    lf, li = logf[:n].cpu().numpy(), logi[:n].cpu().numpy()
-    log = {"loss": lf[:, 0], "mse": lf[:, 1], "kls": lf[:, 2:2 + L], "colls_loss": lf[:, 2 + L:2 + 2 * L], "eq": li[:, 0],
-           "sse": li[:, 1], "counter": li[:, 2], "saved": li[:, 3].astype(bool), "stopper_fired": li[:, 4].astype(bool),
-           "zero_stop": li[:, 5].astype(bool), "used": li[:, 6:].reshape(n, Kc, L)}
-    log["psnr"] = np.array([float(psnr_from_sums(s, image.n_elems, image.peak_term)) for s in log["sse"]], dtype=np.float64)
-    log["accuracy"] = np.array([float((q / image.n_elems) * 100) for q in log["eq"]], dtype=np.float64)
-    return FitResult(log, last_epoch, best_epoch, STOP_REASONS[int(st["reason"])], best, issued, restored)
+        if loop.stop():
+            break
+    return loop.result()
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -1673,25 +1718,6 @@ def score_psnr(net, image, *, step=1, denom=None):
     return psnr_accuracy_from_sums(eq, sse, scored_elements(h, w, C, step), int(img.max()))
 
 
-def _capture_guarded(body):
-    """(graph, body()) with body's launches captured into a torch.cuda.CUDAGraph.  NOT a second policy: this repeats, line for
-    line, the guard of GraphedStep._capture — no garbage collection while the stream captures (a finaliser that touches the
-    runtime during a capture aborts the process), capture_error_mode thread_local — for a body that is not a training step
-    (a captured score()).  Whoever changes one changes the other; folding _capture onto this helper is left to a change that
-    may touch the training step.  Warm body up eagerly first: what it allocates must exist before the capture."""
-    import gc
-    g = torch.cuda.CUDAGraph()
-    gc_was_on = gc.isenabled()
-    gc.disable()
-    try:
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            result = body()
-    finally:
-        if gc_was_on:
-            gc.enable()
-    return g, result
-
-
 def fit_sampled(net, loss_fn, optimizer, sampler, *, rounds, steps_per_round, tolerance, min_delta, should_reset=True, l_mse,
                 l_js_kl, l_collisions, score_step=1, graph=True, poll_every=16, exact_final=True, after_round=None):
     """fit() for batches a data.ImageSampler draws: a round is steps_per_round steps of train_sampled, then score(net, sampler,
@@ -1724,53 +1750,20 @@ def fit_sampled(net, loss_fn, optimizer, sampler, *, rounds, steps_per_round, to
         raise ValueError(refusal)
     dev = img.device
     peak_term = 20 * np.log10(np.uint8(int(img.max())))          # (one read, before the loop)
-    L = net._num_levels
-    nverts = torch.from_numpy(np.asarray(net._level_vertex_counts(), dtype=np.int64)).to(dev)
-    state = torch.from_numpy(new_epoch_state(sse_limit0(n_elems, peak_term)).reshape(1).view(np.uint8).copy()).to(dev)
-    flags = state.view(torch.int32)
-    take, last, finished = flags[0:1], flags[1:2], flags[2:3]
-    polled = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
+    loop = _EpochLoop(net, optimizer, dev, limit=rounds, n_elems=n_elems, peak_term=peak_term, poll_every=poll_every,
+                      exact_final=exact_final, hash_source=net._hash_mode, tolerance=tolerance, min_delta=min_delta,
+                      should_reset=should_reset)
     sums = torch.zeros((2,), dtype=torch.int64, device=dev)
-    logf = torch.full((rounds, 2 + 2 * L), float("nan"), dtype=torch.float64, device=dev)
-    logi = torch.zeros((rounds, 6), dtype=torch.int64, device=dev)
-    best = final = None
-    issued = 0
     for r in range(rounds):
         rec = train_sampled(net, loss_fn, optimizer, sampler, steps_per_round, l_mse=l_mse, l_js_kl=l_js_kl,
                             l_collisions=l_collisions, graph=graph)
-        if best is None:
-            # the optimizer's state exists now (the first step has run): the shadows are allocated once, here
-            tensors = state_tensors(net, optimizer)
-            best = DeviceSnapshot(tensors)
-            final = DeviceSnapshot(tensors) if exact_final else None
         score(net, sampler, step=score_step, out=sums)
-        ops.epoch_tail(state, logf, logi, rec["loss"], rec["mse"], None, None, sums, None, nverts, hash_source=net._hash_mode,
-                       tolerance=tolerance, min_delta=min_delta, should_reset=should_reset, epochs=rounds)
-        best.take_if(take)
-        if final is not None:
-            final.take_if(last)
-        issued = r + 1
+        loop.tail(rec["loss"], rec["mse"], None, None, sums, None)
         if after_round is not None:
             after_round(r, rec)
-        if issued % poll_every == 0 or issued == rounds:
-            polled.copy_(finished, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            if int(polled[0]) != 0:
-                break
-    st = state.cpu().numpy().view(EPOCH_STATE)[0]
-    last_epoch, best_epoch = int(st["last_epoch"]), int(st["best_epoch"])
-    restored = False
-    if issued > last_epoch + 1 and final is not None:
-        final.restore()
-        restored = True
-    n = last_epoch + 1
-    lf, li = logf[:n].cpu().numpy(), logi[:n].cpu().numpy()
-    log = {"loss": lf[:, 0], "mse": lf[:, 1], "kls": lf[:, 2:2 + L], "colls_loss": lf[:, 2 + L:2 + 2 * L], "eq": li[:, 0],
-           "sse": li[:, 1], "counter": li[:, 2], "saved": li[:, 3].astype(bool), "stopper_fired": li[:, 4].astype(bool),
-           "zero_stop": li[:, 5].astype(bool), "used": li[:, 6:].reshape(n, 0, L)}
-    log["psnr"] = np.array([float(psnr_from_sums(s, n_elems, peak_term)) for s in log["sse"]], dtype=np.float64)
-    log["accuracy"] = np.array([float((q / n_elems) * 100) for q in log["eq"]], dtype=np.float64)
-    return FitResult(log, last_epoch, best_epoch, STOP_REASONS[int(st["reason"])], best, issued, restored)
+        if loop.stop():
+            break
+    return loop.result()
 
 
 # ------------------------------------------------------------------------------------------------------------------------

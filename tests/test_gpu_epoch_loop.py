@@ -21,7 +21,7 @@ def _t(a, dtype=None):
 
 
 def _device_state(train, limit):
-    return torch.from_numpy(train.new_epoch_state(limit).reshape(1).view(np.uint8).copy()).to(DEV)
+    return train.epoch_state_tensor(limit, DEV)
 
 
 def _host_state(train, state):

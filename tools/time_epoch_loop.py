@@ -149,7 +149,7 @@ def measure(mode, a, dev, folder):
     out["kernels"]["snapshot_if_not_taken"] = device_events(lambda: snap.take_if(flag), 5, 25)
     out["kernels"]["snapshot_if_taken"]["GBps_read_plus_written"] = 2 * snap.bytes / (out["kernels"]["snapshot_if_taken"]["median_ms"] * 1e6)
     L = c["L"]
-    state = torch.from_numpy(train.new_epoch_state(10 ** 12).reshape(1).view(np.uint8).copy()).to(dev)
+    state = train.epoch_state_tensor(10 ** 12, dev)
     n_tail = 64
     logf = torch.zeros((n_tail * 40, 2 + 2 * L), dtype=torch.float64, device=dev)
     logi = torch.zeros((n_tail * 40, 6 + L), dtype=torch.int64, device=dev)
